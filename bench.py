@@ -5,7 +5,11 @@ shard of packed struct-of-arrays in host memory to the node's verdict
 records -- lc_check_node_async, two steps in flight (H2D -> search -> verdict
 records -> all-gather of every rank's records over RCCL -> records in
 page-locked host memory; each step's upload overlaps the search before it),
-K steps between barriers, the slowest rank's time.  Reported beside it:
+K steps between barriers, the slowest rank's time.  A plain run does that
+and no more: set-up, warm-up, the K timed steps, the result line (and
+--dump-outputs DIR: the verdict fields of the last timed step, per key, as
+DIR/valid.npy, cause.npy and fail_event.npy).  Everything below that takes
+runs of its own is measured with --full only.  Reported beside `value` then:
 `resident` (the same step with the shard already resident in HBM when the
 timed region starts: lc_check_node_device, asynchronous, HIP-event span per
 launch -- the kernel-side rate, never `value`), `d1_pipelined` (the same
@@ -16,9 +20,9 @@ set tiers come from those synchronous steps).
 Workloads (BASELINE.json configs; synthetic, liblincheck's seeded generator):
   N = 1 (default): C2, 1,000 keys x 1,000 client ops, concurrency 10,
         cas-register over values 0..4 (etcdemo.clj:67-69), seed 2 -- the
-        `value`.  The same run then checks C3's whole key space on this one
-        GPU (`c3_strong`: the N = 1 point of the 2/4/8-GPU curve, measured by
-        the same command; --no-c3 skips it).
+        `value`.  With --full the same run then checks C3's whole key space
+        on this one GPU (`c3_strong`: the N = 1 point of the 2/4/8-GPU curve,
+        measured by the same command; --no-c3 skips it).
   N > 1 (default): C3, 100,000 keys x 2,000 ops in total, concurrency 10,
         contiguous key shards, one per rank (strong scaling).
   --config C1|C4|C5 select the others (C1: history.edn -> result map, the
@@ -27,7 +31,7 @@ Every line carries the host marshalling cost beside the step: `pack_ms` /
 `pack_ops_per_s` time lc_pack alone (history -> packed SoA)
 on the history the step consumes; `synth_s` is the generator's time.
 
-Also reported (one JSON line on rank 0):
+Also reported with --full (one JSON line on rank 0):
   roofline      the dominant kernel's algorithmic HBM bytes per launch over
                 its average HIP-event launch time in the timed steps
                 (DESIGN.md section 5), MI355X peak 8 TB/s; traffic from
@@ -92,6 +96,12 @@ def parse():
     ap.add_argument("--config", default=None, choices=sorted(CONFIGS),
                     help="default: C2 at one GPU, C3 (strong scaling) at more")
     ap.add_argument("--budget", type=int, default=1 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the synchronous and resident "
+                         "steps, the roofline's per-launch times, probe counts, the CPU baselines and parity "
+                         "with the oracle, c3_strong (each still skipped by its own --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline")
     ap.add_argument("--cpu-full", action="store_true",
                     help="time the CPU :wgl restatement on the whole batch, not a bounded sample")
@@ -109,7 +119,39 @@ def parse():
     ap.add_argument("--ops", type=int, default=0, help="override ops per key (exploration only)")
     ap.add_argument("--path-flags", type=lambda x: int(x, 0), default=0,
                     help="lc_opts.path_flags (LC_PATH_*) of the step: pinned path choices for A/B runs only")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the line
+        args.no_cpu = args.no_resident = args.no_probes = args.no_c3 = True
+    return args
+
+
+DUMP_LIMIT = 64_000_000  # bytes --dump-outputs may write in all
+
+
+def dump_outputs(path, arrays):
+    """Write equal-length per-key arrays as path/<name>.npy in float64 (every
+    field of a verdict record is below 2^48, so exact).  Past DUMP_LIMIT a
+    fixed, seeded sample of the rows is written, its row numbers beside it
+    as sample_index.npy."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.asarray(v).astype(np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    rows = (DUMP_LIMIT // (len(arrays) + 1) - 128) // 8  # (128: a .npy header)
+    if n > rows:
+        idx = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
+def result_map_arrays(out):
+    """The per-key verdicts of an independent/checker result map, keys in
+    sorted order: valid 1 / 0 / -1 (:unknown)."""
+    keys = sorted(out["results"])
+    valid = [{True: 1, False: 0}.get(out["results"][k].get("valid?"), -1) for k in keys]
+    return {"keys": [int(k) for k in keys], "valid": valid}
 
 
 def host_cores():
@@ -185,6 +227,8 @@ def bench_c1(args):
         "step": "lc_edn_read + independent/checker(compose(linearizable, timeline)) -> result map",
         "valid?": out["valid?"], "failures": out["failures"], "parity_vs_oracle": parity,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_map_arrays(out))
     print(json.dumps(line, default=str), flush=True)
 
 
@@ -260,6 +304,8 @@ def bench_jepsen(args):
         "failures_equal_oracle": parity,
         "roofline": None, "cpu_baseline": None,
     }
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_map_arrays(out))
     print(json.dumps(line, default=str), flush=True)
 
 
@@ -659,9 +705,10 @@ def main():
     if pipelined:
         elapsed, rec = timed(d1_pipe_step)
         n_pipe = n_enq[0]
-        el_s, rec_s = timed(d1_step)
-        d1_sync = {"ms_per_step": el_s / args.steps * 1e3, "elapsed_s": el_s,
-                   "pipelined_steps": n_pipe, "same_records": bool(np.array_equal(rec, rec_s))}
+        if args.full:
+            el_s, rec_s = timed(d1_step)
+            d1_sync = {"ms_per_step": el_s / args.steps * 1e3, "elapsed_s": el_s,
+                       "pipelined_steps": n_pipe, "same_records": bool(np.array_equal(rec, rec_s))}
     else:
         elapsed, rec = timed(d1_step)
     node = node_records(rec.copy())
@@ -708,7 +755,10 @@ def main():
             shards = [np.arange(r * K, (r + 1) * K) for r in range(world)]
         # the node's verdicts from its gathered blocks (rank order, padding 0),
         # back in the key space's order
-        nv, _, nfe = P.node_key_order(node, shards, block)
+        nv, ncause, nfe = P.node_key_order(node, shards, block)
+        if args.dump_outputs:
+            # the node's records of the last timed step, field by field in key order
+            dump_outputs(args.dump_outputs, {"valid": nv, "cause": ncause, "fail_event": nfe})
         v_host, fe_host = nv[shards[0]], nfe[shards[0]]  # rank 0's own shard
         n_keys_total = int(nv.size)
         decided = int(((nv == 1) | (nv == 0)).sum())
@@ -771,7 +821,7 @@ def main():
         if args.algorithm != "linear":
             # knossos.wgl's walk (k_wgl) and what it moved: one batch check
             # for the per-key cache sizes and the walk's steps
-            wres = dev.check(packed) if world == 1 else None
+            wres = dev.check(packed) if world == 1 and args.full else None
             wsel = (wres.analyzer == 1) if wres is not None else None
             cache_entries = int(wres.peak[wsel].sum()) if wres is not None else None
             wsteps = int(wres.stats["wgl_steps"]) if wres is not None else None
@@ -870,7 +920,7 @@ def main():
                          "alg_bytes_per_launch": alg_bytes, "avg_launch_ms": kt, "event_word_bytes": ewb,
                          "traffic_over_alg": (traffic / alg_bytes) if traffic and alg_bytes else None,
                          "traffic_source": traffic_src, "issue": issue, "launch_time_from": t0_src,
-                         "launches": len(d1_t0), "d4_model_gbs": d4_t3},
+                         "launches": len(d1_t0), "d4_model_gbs": d4_t3} if kt > 0 else None,
             "cpu_baseline": cpu,
             "ops_total": ops_total,
             "ops_checked_per_step": ops_checked,

@@ -78,6 +78,36 @@ def test_refuses_mixed_or_chunk_profiles():
     assert bench.profile_mismatch(d, 256, "k_search_layers") is None
 
 
+def test_plain_run_skips_what_full_measures(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_cpu and a.no_resident and a.no_probes and a.no_c3
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-c3"])
+    a = bench.parse()
+    assert a.full and a.no_c3 and not (a.no_cpu or a.no_resident or a.no_probes)
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path, monkeypatch):
+    import numpy as np
+    valid = np.array([1, 0, -1, 1], np.int8)
+    fe = np.array([-1, (1 << 31) - 2, -1, 7], np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), {"valid": valid, "fail_event": fe})
+    got = np.load(tmp_path / "a" / "fail_event.npy")
+    assert got.dtype == np.float64 and np.array_equal(got, fe) and not (tmp_path / "a" / "sample_index.npy").exists()
+    assert np.array_equal(np.load(tmp_path / "a" / "valid.npy"), valid)
+    # past the size limit: the same seeded rows of every array, run after run
+    monkeypatch.setattr(bench, "DUMP_LIMIT", 3 * (8 * 10 + 128))
+    big = np.arange(1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"valid": big % 3, "fail_event": big})
+    idx = np.load(tmp_path / "b" / "sample_index.npy")
+    assert idx.size == 10 and np.array_equal(idx, np.load(tmp_path / "c" / "sample_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "b" / "fail_event.npy"), idx)
+    assert np.array_equal(np.load(tmp_path / "b" / "valid.npy"), idx % 3)
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT
+
+
 def test_probe_rates():
     r = bench.probe_rates(1000, 0, 0.5, 0.0, [], None)
     assert r == {"t0": 1000 / 0.5e-3}

@@ -16,7 +16,7 @@ pmc() {  # name kernel workload keys budget algorithm
   local n=$1 k=$2 w=$3 keys=$4 b=$5 alg=$6
   local fc=$(csv f_$n '*counter_collection.csv') wc=$(csv w_$n '*counter_collection.csv')
   local s1=$(csv sq1_$n '*counter_collection.csv') s2=$(csv sq2_$n '*counter_collection.csv')
-  local cmd="rocprofv3 --pmc <counters> -- python3 bench.py (tools/gpu_evidence.sh part $n, R=$R)"
+  local cmd="rocprofv3 --pmc <counters> -- python3 bench.py --full (tools/gpu_evidence.sh part $n, R=$R)"
   [ -n "$fc" ] && [ -n "$wc" ] && python3 tools/profile_summary.py bytes --kernel "$k" --workload $w --keys $keys \
       --budget $b --round $R --algorithm $alg --cmd "$cmd" --out $P/${T}_${n}_pmc.json "$fc" "$wc"
   [ -n "$s1" ] && [ -n "$s2" ] && python3 tools/profile_summary.py sq --kernel "$k" --workload $w --keys $keys \
@@ -27,7 +27,7 @@ pmc() {  # name kernel workload keys budget algorithm
 tr() {  # name kernel workload keys budget algorithm
   local t=$(csv kt_$1 '*kernel_trace.csv')
   [ -n "$t" ] && python3 tools/profile_summary.py trace --kernel "$2" --workload $3 --keys $4 --budget $5 --round $R \
-      --algorithm $6 --cmd "rocprofv3 --kernel-trace --stats -- python3 bench.py (tools/gpu_evidence.sh part $1)" \
+      --algorithm $6 --cmd "rocprofv3 --kernel-trace --stats -- python3 bench.py --full (tools/gpu_evidence.sh part $1)" \
       --out $P/${T}_$1_trace.json "$t"
   return 0
 }

@@ -26,7 +26,7 @@ for r in $(seq 1 ${ROUNDS:-1}); do
   for w in ${WORKLOADS:-c2}; do
     for v in ${VARIANTS:-base}; do
       echo "== $w $v round $r $(date +%T)"
-      LINCHECK_LIB_OVERRIDE=$(lib $v) timeout -k 10 ${LIMIT:-300} python -u bench.py $(args $w) ${EXTRA:-} > $O/${w}_${v}_$r.json 2> $O/${w}_${v}_$r.err || { tail -5 $O/${w}_${v}_$r.err; exit 1; }
+      LINCHECK_LIB_OVERRIDE=$(lib $v) timeout -k 10 ${LIMIT:-300} python -u bench.py --full $(args $w) ${EXTRA:-} > $O/${w}_${v}_$r.json 2> $O/${w}_${v}_$r.err || { tail -5 $O/${w}_${v}_$r.err; exit 1; }
       ms $O/${w}_${v}_$r.json
     done
   done

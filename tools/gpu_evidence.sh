@@ -21,21 +21,21 @@ SQ2="SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_
 bench() {  # name limit args...
   local n=$1 lim=$2; shift 2
   step bench_$n
-  timeout -k 10 $lim python -u bench.py "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { tail -5 $O/bench_$n.err; exit 1; }
+  timeout -k 10 $lim python -u bench.py --full "$@" > $O/bench_$n.json 2> $O/bench_$n.err || { tail -5 $O/bench_$n.err; exit 1; }
   cut -c1-300 $O/bench_$n.json
 }
 prof() {  # name limit bench args: kernel trace + stats
   local n=$1 lim=$2; shift 2
   step prof_$n
-  timeout -k 10 $lim rocprofv3 --kernel-trace --stats -d $O/prof/kt_$n -o kt --output-format csv -- python3 bench.py "$@" > $O/prof/kt_$n.log 2>&1 || { tail -20 $O/prof/kt_$n.log; exit 1; }
+  timeout -k 10 $lim rocprofv3 --kernel-trace --stats -d $O/prof/kt_$n -o kt --output-format csv -- python3 bench.py --full "$@" > $O/prof/kt_$n.log 2>&1 || { tail -20 $O/prof/kt_$n.log; exit 1; }
 }
 pmc() {  # name bench args: 4 counter passes, each its own run
   local n=$1; shift
   step pmc_$n
-  timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d $O/prof/f_$n -o f --output-format csv -- python3 bench.py "$@" > $O/prof/f_$n.log 2>&1 || { tail -5 $O/prof/f_$n.log; exit 1; }
-  timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -d $O/prof/w_$n -o w --output-format csv -- python3 bench.py "$@" > $O/prof/w_$n.log 2>&1 || { tail -5 $O/prof/w_$n.log; exit 1; }
-  timeout -s KILL 200 rocprofv3 --pmc $SQ1 -d $O/prof/sq1_$n -o p1 --output-format csv -- python3 bench.py "$@" > $O/prof/sq1_$n.log 2>&1 || { tail -5 $O/prof/sq1_$n.log; exit 1; }
-  timeout -s KILL 200 rocprofv3 --pmc $SQ2 -d $O/prof/sq2_$n -o p2 --output-format csv -- python3 bench.py "$@" > $O/prof/sq2_$n.log 2>&1 || { tail -5 $O/prof/sq2_$n.log; exit 1; }
+  timeout -s KILL 200 rocprofv3 --pmc FETCH_SIZE -d $O/prof/f_$n -o f --output-format csv -- python3 bench.py --full "$@" > $O/prof/f_$n.log 2>&1 || { tail -5 $O/prof/f_$n.log; exit 1; }
+  timeout -s KILL 200 rocprofv3 --pmc WRITE_SIZE -d $O/prof/w_$n -o w --output-format csv -- python3 bench.py --full "$@" > $O/prof/w_$n.log 2>&1 || { tail -5 $O/prof/w_$n.log; exit 1; }
+  timeout -s KILL 200 rocprofv3 --pmc $SQ1 -d $O/prof/sq1_$n -o p1 --output-format csv -- python3 bench.py --full "$@" > $O/prof/sq1_$n.log 2>&1 || { tail -5 $O/prof/sq1_$n.log; exit 1; }
+  timeout -s KILL 200 rocprofv3 --pmc $SQ2 -d $O/prof/sq2_$n -o p2 --output-format csv -- python3 bench.py --full "$@" > $O/prof/sq2_$n.log 2>&1 || { tail -5 $O/prof/sq2_$n.log; exit 1; }
 }
 for part in $PARTS; do
   case $part in

@@ -4,7 +4,7 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 O=gpurun_out/specsq
 mkdir -p $O
-B="python3 bench.py --steps 5 --warmup 1 --no-cpu --no-resident --no-probes"
+B="python3 bench.py --full --steps 5 --warmup 1 --no-cpu --no-resident --no-probes"
 timeout -s KILL 90 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_SALU -d $O/p1 -o p1 --output-format csv -- $B > $O/p1.log 2>&1 || { tail -5 $O/p1.log; exit 1; }
 timeout -s KILL 90 rocprofv3 --pmc SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_SCA SQ_INSTS_LDS SQ_INSTS_VMEM SQ_INSTS_BRANCH SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_MISC SQ_INSTS_SMEM -d $O/p2 -o p2 --output-format csv -- $B > $O/p2.log 2>&1 || { tail -5 $O/p2.log; exit 1; }
 python3 - <<'PY'
