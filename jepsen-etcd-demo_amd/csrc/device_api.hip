@@ -1345,7 +1345,7 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
     // Large batches too (C3 shards: 2 segments per key; 12,500 x 2,000 4.44
     // ms against 5.51 unsegmented, the whole C3 key space 33.2 against 38.0).
     // More segments than waves (a key's waves taking its segments from a
-    // block-local queue, see k_spec) measured slower: C2 8 segments on 4 waves
+    // block-local queue) measured slower: C2 8 segments on 4 waves
     // 0.302 ms, 12 on 4 0.332, against 0.273 for 4 on 4; a C3 shard 4 on 2
     // 4.75 ms, 8 on 2 5.30, against 4.40 for 2 on 2.
     int segs = K > 0 ? (int)std::min<int64_t>(8, (int64_t)c->cu_count * 4 * 4 / std::max<int64_t>(K, 1)) : 0;
@@ -1364,16 +1364,15 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
     if (LC_SPEC8_WAVES >= 8 && (fast || exact_spec) && K > 0 && K * 8 <= (int64_t)c->cu_count * 4 * 8) segs = 8;
     if (o.spec_segs) segs = o.spec_segs;
     if (exact_spec && !fast) segs = segs >= 8 ? 8 : segs >= 4 ? 4 : 2;  // the exact builds
-    const int waves = segs;
     bool spec = !split && t0_step && (fast || exact_spec) && segs >= 2 && !(o.path_flags & LC_PATH_SPEC_OFF);
     // The segments' workspaces are per key: a batch whose keys
     // would need more than SPEC_WS_MAX_BYTES of them takes the unsegmented
     // register tier, whose workspace is per resident wave.
-    if (spec && (uint64_t)(lcd::spec_ws_words(K, waves) + (exact_spec && !fast ? lcd::spec_fin_words(K, segs) : 0)) * 4 >
+    if (spec && (uint64_t)(lcd::spec_ws_words(K, segs) + (exact_spec && !fast ? lcd::spec_fin_words(K, segs) : 0)) * 4 >
                     SPEC_WS_MAX_BYTES)
         spec = false;
     if (spec) {
-        const size_t need = lcd::spec_ws_words(K, waves);
+        const size_t need = lcd::spec_ws_words(K, segs);
         if (need > c->spec_ws_words) {
             if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
             dfree(c->spec_ws);
@@ -1497,14 +1496,14 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
         // the validation of a host-unchecked batch runs in extra blocks of
         // the same launch (a second stream cost ~40 us of cross-stream waits)
         const int vblocks = a.strict ? (int)std::min<int64_t>(K, c->cu_count) : 0;
-        HIPCHK(lcd::launch_spec(a0, dargs, segs, waves, c->spec_ws, c->spec_rr, c->spec_parity, ck1, ck2,
+        HIPCHK(lcd::launch_spec(a0, dargs, segs, c->spec_ws, c->spec_rr, c->spec_parity, ck1, ck2,
                                 // (rerun blocks: the launch usually finds no
                                 // key, so one block per CU keeps its dispatch
                                 // short; a longer rerun list walks the grid)
                                 LC_SPEC_RERUN_BLOCKS > 0 ? LC_SPEC_RERUN_BLOCKS : c->cu_count, vblocks, ev16,
                                 (o.path_flags & LC_PATH_SPEC_COST) != 0,
                                 !(o.path_flags & LC_PATH_SPEC_NOPRIO),
-                                K * waves > (int64_t)c->cu_count * 16,  // more keys than one resident round
+                                K * segs > (int64_t)c->cu_count * 16,  // more keys than one resident round
                                 exact_spec && !fast ? c->spec_fin : nullptr,
                                 !(o.path_flags & LC_PATH_SPEC_NOSTAGE), c->stream));
         c->spec_parity ^= 1;

@@ -306,8 +306,8 @@ struct T0Args {
     uint32_t *spec_fin;          // exact segments: each run's saved set (2 per segment, SPEC_SAVE_WORDS each)
 };
 
-// T0Args read through the kernarg segment where a field is used (k_spec,
-// LC_SPEC_KARG): a kernel that takes its arguments by value loads every field
+// T0Args read through the kernarg segment where a field is used (k_spec's
+// KA): a kernel that takes its arguments by value loads every field
 // it uses anywhere at its entry and holds it in a scalar register for its
 // whole life; with the walk's own scalars the file overflows into VGPR lanes
 // and uniform loop words are kept in VGPRs (copied at every event).  The empty
@@ -2079,9 +2079,6 @@ constexpr uint32_t SPEC_SAVE_WORDS = (T0_RMEM + 2) * 64;
 // phase, for steps that report final configs; `save` (EX, may be null)
 // receives the run's set at its end or before its failing :ok, in the
 // LatMem row layout write_final_mem reads, with its slots and live indices.
-#ifndef LC_SPEC_CK_SPLIT
-#define LC_SPEC_CK_SPLIT 1
-#endif
 // Checkpoints of a TOP run: at ck1, ck2 and evenly between (a verifying run
 // compares its set at each and stops at the first match; one that passes
 // them all unmet sends the key to the unsegmented search).  A third one
@@ -2106,7 +2103,7 @@ __device__ __forceinline__ uint32_t spec_ck_target(uint32_t i, uint32_t ck1, uin
 // Flags between the waves of one k_spec workgroup (LDS, workgroup scope).  A
 // wave publishes after its stores (a release fence for the whole wave, then
 // lane 0's store); a waiter polls with an acquire load and sleeps between
-// polls, a fixed trip count over a uniform value (the queue loops' rule
+// polls, a fixed trip count over a uniform value (k_spec's INVARIANT
 // below).  The wait is bounded: a waiter that gives up takes the exact path
 // (the key is searched unsegmented), so a timeout costs time, never a result.
 constexpr uint32_t SPEC_WAIT_MAX = 1u << 22;
@@ -2126,8 +2123,8 @@ __device__ __forceinline__ bool spec_wait(const int32_t *f) {
     return false;
 }
 // A verifying run's checkpoint event i (relative to nothing: the event
-// index), read while the TOP run it compares with may still be walking
-// (LC_SPEC_OVERLAP): waits until that run has recorded it or has ended
+// index), read while the TOP run it compares with may still be walking:
+// waits until that run has recorded it or has ended
 // without it (-1: no such checkpoint); -1 on a timeout too.
 __device__ __forceinline__ int32_t spec_ck_event(const int32_t *ck_e, uint32_t i, const int32_t *top_done) {
     if (!top_done) return uni(ck_e[i]);
@@ -2175,15 +2172,10 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
     uint32_t ev_nn = 128 + lane < nev ? ep[128 + lane] : 0u;
     Xfer xc = xfer_of(dsc);
     uint32_t e = 0, i = 0, base = 0, lim = nev;
-    // progress steps of the walk (its priority steps down at each)
-#ifndef LC_SPEC_PRIO_STEPS  // diagnostic builds: 1 = at 1/2, 3/4 and 7/8 of the walk
-#define LC_SPEC_PRIO_STEPS 0
-#endif
-#if LC_SPEC_PRIO_STEPS == 1
-    const uint32_t q1 = nev / 2u, q2 = nev - nev / 4u, q3 = nev - nev / 8u;
-#else
+    // progress steps of the walk (its priority steps down at each): its
+    // quarters; steps at 1/2, 3/4 and 7/8 measured no different (DESIGN.md,
+    // "Issue priority by progress")
     const uint32_t q1 = nev / 4u, q2 = nev / 2u, q3 = nev - nev / 4u;
-#endif
     if (MODE == 0 && prio) spec_prio(0);
     auto advance = [&]() {
         ++e;
@@ -2207,8 +2199,10 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
     bool dirty = true;
     // One lane-phase event (<= 6 pending); true: an :invoke with 6 pending,
     // for the dense phase.  CK: the event may be a checkpoint's :ok.  The
-    // events before the next checkpoint run the body without that test
-    // (LC_SPEC_CK_SPLIT), so the checkpoint words stay out of the hot loop.
+    // events before the next checkpoint run the body without that test, so
+    // the checkpoint words stay out of the hot loop (one body for both
+    // measured C2 0.2655 against 0.2596 ms: DESIGN.md, "The lane phase split
+    // at the checkpoints").
     auto lane_event = [&](auto ck_t) -> bool {
         constexpr bool CK = decltype(ck_t)::value;
         const uint32_t evi = __builtin_amdgcn_readlane(ev, i);
@@ -2293,14 +2287,12 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
     for (uint32_t phase = 0; phase <= nev && e < lim; ++phase) {
         bool dense = false;
         while (e < lim) {  // lane phase: <= 6 pending
-#if LC_SPEC_CK_SPLIT
             uint32_t stop = min(lim, ck_at);
             while (e < stop) {
                 if (lane_event(std::false_type{})) { dense = true; break; }
                 stop = min(stop, lim);
             }
             if (dense || e >= lim) break;
-#endif
             if (lane_event(std::true_type{})) { dense = true; break; }
         }
         (void)dense;
@@ -2422,26 +2414,13 @@ extern "C" int lc_debug_spec_stamps(unsigned long long *host, int n) {
 #define SPEC_STAMP(s, k, v)
 #endif
 
-// Checked builds only (LC_SPEC_CHECK_UNIFORM): a queue index that is not
-// wave-uniform refuses the batch instead of walking on a divergent index.
-#ifdef LC_SPEC_CHECK_UNIFORM
-#define SPEC_CHECK_UNIFORM(x)                                                        \
-    if (__any((x) != (uint32_t)__builtin_amdgcn_readfirstlane(x)) && lane == 0) {  \
-        atomicOr(&a.err[0], (int32_t)LC_BATCH_E_FIT);                              \
-        atomicMax(&a.err[1], a.err_base + key + 1);                                \
-    }
-#else
-#define SPEC_CHECK_UNIFORM(x)
-#endif
-
-// One workgroup of W waves per key (blockIdx = LPT position), the key cut into
-// up to S segments; the waves take the segments' TOP walks, then their
-// verifying runs, from two block-local queues (launched with S = W: more
-// segments than waves, a wave taking another walk instead of waiting at the
-// barrier for the slowest, measured slower -- every extra cut costs a
-// verifying run and a walk's start-up).  Results go through a.full like
-// T0's; a.lat_ws holds each wave's 9-10-pending fallback workspace (global
-// memory: the workgroup's LDS workspaces are shared, NWS of them).
+// One workgroup per key (blockIdx = LPT position), the key cut into up to S
+// segments, one wave per segment: wave w walks segment w from TOP, then
+// verifies the next kept segment from the set its walk ended with, and wave 0
+// gives the key's verdict ("Speculative key segments").  Results go
+// through a.full like T0's; a.lat_ws holds each wave's 9-10-pending fallback
+// workspace (global memory: the workgroup's LDS workspaces are shared, NWS of
+// them).
 // 16-bit event words of a key k_spec stages in LDS: none for 2-segment
 // workgroups (the many-key batches, where 6 KB more per block would cost
 // occupancy), 4,096 (8 KB) otherwise -- C2's keys have ~1,470.  (The 8-wave
@@ -2450,9 +2429,6 @@ extern "C" int lc_debug_spec_stamps(unsigned long long *host, int n) {
 template <int S, bool E16>
 constexpr uint32_t spec_ev_lds() { return (E16 && S > 2) ? (S >= 8 && SPEC_NCK > 2 ? 3072u : 4096u) : 0u; }
 
-#ifndef LC_SPEC_KARG
-#define LC_SPEC_KARG 1
-#endif
 // The 2-wave build (the many-key batches: C3's shards, throughput-bound) is
 // held to 8 waves per SIMD: 64 VGPRs, 140 B per lane spilled to scratch, and
 // no LDS workspace (LC_SPEC2_NWS) so that 8 fit.  A/B on one box, the C3
@@ -2463,13 +2439,12 @@ constexpr uint32_t spec_ev_lds() { return (E16 && S > 2) ? (S >= 8 && SPEC_NCK >
 #ifndef LC_SPEC2_WAVES
 #define LC_SPEC2_WAVES 8
 #endif
-template <int S, int W, bool E16, bool EX = false>
-__global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC8_WAVES : 1)) void k_spec(T0Args a) {
-#if LC_SPEC_KARG
+template <int S, bool E16, bool EX = false>
+__global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC8_WAVES : 1)) void k_spec(T0Args a) {
+// a's fields, read through the kernarg segment at each use (t0k): no faster
+// than reading `a` (C2 0.2739 / 0.2732 ms), but half the scalar spills
+// ("k_spec's arguments through the kernarg segment").
 #define KA t0k()
-#else
-#define KA a
-#endif
     constexpr uint32_t EVC = spec_ev_lds<S, E16>();
     __shared__ uint16_t s_ev[EVC ? EVC : 1];  // the key's event words (EvStaged)
     __shared__ uint32_t s_end[S][64];     // TOP run's set at the segment's end
@@ -2482,10 +2457,9 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
     __shared__ int32_t s_ver[S], s_vfev[S];
     __shared__ int32_t s_net[S];          // cut search: pending-count change over each part
     __shared__ int32_t s_cand[S], s_ncand[S];  // each target's cut (-1: none) and ops pending there
-    __shared__ int32_t s_next[2];         // the block's queues: TOP walks, verifying runs
-    __shared__ int32_t s_prdy[S], s_done[S];  // LC_SPEC_OVERLAP: s_pend / s_top -3 of s out; TOP run of s ended
-    __shared__ uint32_t s_vx[W][2];       // self-validation: each wave's part, XOR of its slots' one-hots
-    constexpr int NWS = spec_lds_ws<W>();
+    __shared__ int32_t s_prdy[S], s_done[S];  // flags a verifying wave waits on: s_pend / s_top -3 of s out; TOP run of s ended
+    __shared__ uint32_t s_vx[S][2];       // self-validation: each wave's part, XOR of its slots' one-hots
+    constexpr int NWS = spec_lds_ws<S>();
     __shared__ uint32_t s_ws[NWS ? NWS * 3 * T0_RMEM * 64 : 1];  // 9-10-pending workspaces (12 KB each)
     __shared__ int32_t s_ws_busy[NWS ? NWS : 1];
     const uint32_t lane = lane_id(), wv = uni((uint32_t)threadIdx.x >> 6);  // uniform per wave
@@ -2497,7 +2471,7 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
     const uint32_t blk = vfirst ? blockIdx.x - nb : blockIdx.x;  // the key block's LPT position
     if (vfirst ? blockIdx.x < nb : blockIdx.x >= (uint32_t)KA.n_order) {
         const uint32_t vb = vfirst ? blockIdx.x : blockIdx.x - (uint32_t)KA.n_order;
-        for (int64_t k = (int64_t)vb * W + wv; k < KA.n_order; k += (int64_t)nb * W) {
+        for (int64_t k = (int64_t)vb * S + wv; k < KA.n_order; k += (int64_t)nb * S) {
             // (a key whose words its own block stages whole is validated
             // there, from LDS: see below)
             if (EVC > 0 && !(KA.flags & T0_SPEC_NOSTAGE) && KA.ev_off[k + 1] - KA.ev_off[k] <= EVC) continue;
@@ -2505,17 +2479,12 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         }
         return;  // the whole block: no barrier below is reached by half of it
     }
-    // The block's set-up -- staging, validation, the cuts -- at a TOP walk's
-    // first-quarter issue priority (LC_SPEC_CUT_PRIO=1, A/B): measured in
-    // round 6 at -0.3 % on C2 / C5 and other seeds (tools/gpu_r6n.sh,
-    // profiles/r06_segments_seeds.txt), within noise; not the default.
-#ifndef LC_SPEC_CUT_PRIO
-#define LC_SPEC_CUT_PRIO 0
-#endif
-    if (LC_SPEC_CUT_PRIO && !(KA.flags & T0_SPEC_NOPRIO)) __builtin_amdgcn_s_setprio(3);
+    // (The block's set-up -- staging, validation, the cuts -- runs at issue
+    // priority 0: at a TOP walk's first-quarter priority it measured -0.3 % on
+    // C2 / C5 and other seeds, within noise, profiles/r06_segments_seeds.txt.)
     // (scalar: as a VGPR it was the 64-VGPR builds' last spill to scratch)
     const int32_t key = (int32_t)uni((uint32_t)KA.order[blk]);
-    uint32_t *ws = KA.lat_ws + ((size_t)blk * W + wv) * (3 * T0_RMEM * 64);
+    uint32_t *ws = KA.lat_ws + ((size_t)blk * S + wv) * (3 * T0_RMEM * 64);
     const uint64_t eb = KA.ev_off[key];
     const uint32_t nev = (uint32_t)(KA.ev_off[key + 1] - eb);
     // the key's words: staged in LDS (8 loads in flight per thread, then the
@@ -2525,16 +2494,16 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         if (!(KA.flags & T0_SPEC_NOSTAGE)) {
             n_lds = nev < EVC ? nev : EVC;
             const uint16_t *g = KA.events16 + eb;
-            for (uint32_t base = 0; base < n_lds; base += 64u * W * 8u) {
+            for (uint32_t base = 0; base < n_lds; base += 64u * S * 8u) {
                 uint16_t v[8];
 #pragma unroll
                 for (uint32_t q = 0; q < 8; ++q) {
-                    const uint32_t j = base + q * 64u * W + threadIdx.x;
+                    const uint32_t j = base + q * 64u * S + threadIdx.x;
                     v[q] = j < n_lds ? g[j] : (uint16_t)0;
                 }
 #pragma unroll
                 for (uint32_t q = 0; q < 8; ++q) {
-                    const uint32_t j = base + q * 64u * W + threadIdx.x;
+                    const uint32_t j = base + q * 64u * S + threadIdx.x;
                     if (j < n_lds) s_ev[j] = v[q];
                 }
             }
@@ -2557,10 +2526,9 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
     const uint32_t topmask = nstates >= 32 ? ~0u : (1u << nstates) - 1u;
 
     if (threadIdx.x < NWS) s_ws_busy[threadIdx.x] = 0;
-    if (threadIdx.x < 2) s_next[threadIdx.x] = 0;
     __syncthreads();
     // T0_STRICT batches whose key the block staged whole: the key's
-    // validation here, from LDS, its 64-event chunks split over the W waves
+    // validation here, from LDS, its 64-event chunks split over the S waves
     // (the slot protocol's state at a wave's first chunk is the XOR of the
     // earlier waves' slot parities, exchanged at the cut search's barrier),
     // instead of a second HBM read of the words in the validation blocks.
@@ -2570,8 +2538,8 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         self_val = (KA.flags & T0_STRICT) && !(KA.flags & T0_SPEC_NOSTAGE) && n_lds == nev &&
                    !(KA.key_error && KA.key_error[key]);
         const uint32_t nch = (nev + 63u) / 64u;
-        vc0 = nch * wv / W;
-        vc1 = nch * (wv + 1u) / W;
+        vc0 = nch * wv / S;
+        vc1 = nch * (wv + 1u) / S;
         if (self_val) {
             uint32_t x0 = 0, x1 = 0;
             for (uint32_t ch = vc0; ch < vc1; ++ch) {
@@ -2594,11 +2562,11 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
     // estimated cost, each wave computing every target); each moved to the
     // boundary with the fewest ops pending within 64 events.  Equal event
     // counts: the waves count the pending-count change over the parts
-    // [t_p, t_p+1) (part p on wave p mod W), the parts' prefix gives the count
+    // [t_p, t_p+1) (part p on wave p mod S), the parts' prefix gives the count
     // at each target, and the waves place the cuts likewise -- two barriers.
     const bool cost = (KA.flags & T0_SPEC_COST) != 0;
     if (!plain && !cost) {
-        for (uint32_t p = wv; p + 1 < eff; p += W) {
+        for (uint32_t p = wv; p + 1 < eff; p += S) {
             const uint32_t t0 = (uint32_t)((uint64_t)nev * p / eff), t1 = (uint32_t)((uint64_t)nev * (p + 1) / eff);
             const int32_t d = spec_net(evp, t0, t1);
             if (lane == 0) s_net[p] = d;
@@ -2625,7 +2593,7 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         }
     }
     if (!plain && !cost) {
-        for (uint32_t s = wv; s < eff; s += W) {
+        for (uint32_t s = wv; s < eff; s += S) {
             if (s == 0) continue;
             int32_t pend = 0;
             for (uint32_t q = 0; q < s; ++q) pend += uni(s_net[q]);
@@ -2643,7 +2611,7 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         uint32_t pos_v;
         int32_t pend_v;
         spec_targets_cost(evp, nev, eff, pos_v, pend_v);
-        for (uint32_t s = wv; s < eff; s += W) {  // every wave has every target: each places its own cuts
+        for (uint32_t s = wv; s < eff; s += S) {  // every wave has every target: each places its own cuts
             if (s == 0) continue;
             const uint32_t t = uni(__builtin_amdgcn_readlane(pos_v, s));
             const uint32_t w = t + lane < nev ? evp[t + lane] : 0u;
@@ -2682,136 +2650,23 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
         }
     }
     __syncthreads();
-#ifndef LC_SPEC_OVERLAP
-#define LC_SPEC_OVERLAP 1
-#endif
-    if constexpr (LC_SPEC_OVERLAP && S == W) {
-        // 1 + 2, overlapped (LC_SPEC_OVERLAP): wave w walks segment w from
-        // TOP, then at once verifies the next kept segment from the set its
-        // own walk ended with -- without waiting at a barrier for every TOP
-        // walk of the block.  The verifying run compares with that segment's
-        // TOP run at its checkpoints, which that run publishes as it passes
-        // them (spec_ck_event waits for one not reached yet), and with its end
-        // set once it has ended.  A block then takes about its slowest TOP
-        // walk, not its slowest TOP walk plus its slowest verifying run.
-        if (!plain) {
-            const uint32_t s = wv;
-            const bool kept = s < eff && uni(s_cut[s]) >= 0;
-            int32_t top_s = -1;
-            if (kept) {
-                const int32_t cut_i = uni(s_cut[s]);
-                const uint32_t cut = (uint32_t)cut_i, end = (uint32_t)uni(s_segend[s]);
-                const uint32_t n0 = s == 0 ? 0u : (uint32_t)uni(s_ncand[s]);
-                SPEC_STAMP(s, 1, __builtin_amdgcn_s_memtime())
-                SPEC_STAMP(s, 6, ((unsigned long long)end << 32) | cut)
-                SPEC_STAMP(s, 8, (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4) |
-                                     ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32))
-                SPEC_STAMP(s, 9, (unsigned long long)key)
-                SpecState st{};
-                uint32_t words = 0, np = 0;
-                if (s == 0) {
-                    st.W0 = lane == 0 ? 1u << KA.init_state : 0u;
-                } else {
-                    words = spec_pending(evp, cut, n0, np);
-                    spec_setup(st, words, np, trp, ntr);
-                    st.W0 = lane < (1u << np) ? topmask : 0u;
-                }
-                if (lane < 6) s_pend[s][lane] = words;
-                if (lane == 6) s_pend[s][6] = np;
-                const bool lost = s != 0 && np != n0;
-                if (lost && lane == 0) s_top[s] = -3;
-                spec_publish(&s_prdy[s]);
-                uint32_t fev = 0;
-                uint32_t *const sv = EX ? KA.spec_fin + ((size_t)blk * S + s) * 2 * SPEC_SAVE_WORDS : nullptr;
-                const int r = lost ? 6
-                                   : spec_walk<0, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
-                                                                       s_ck[s], s_ck_e[s], KA.spec_ck1, KA.spec_ck2,
-                                                                       fev, !(KA.flags & T0_SPEC_NOPRIO), sv);
-                s_end[s][lane] = st.W0;
-                uint64_t map = 0;
-                for (uint32_t q = 0; q < 6; ++q) {
-                    const uint32_t sl = __builtin_amdgcn_readlane(st.slot_v, q);
-                    if ((st.live >> q) & 1u) map |= (uint64_t)(0x80u | sl) << (8 * q);
-                }
-                SPEC_STAMP(s, 2, __builtin_amdgcn_s_memtime())
-                top_s = r == 1 ? (int32_t)fev : r == 3 ? -2 : r == 6 ? -3 : -1;
-                if (lane == 0) {
-                    s_map[s] = map;
-                    s_top[s] = top_s;
-                }
-                spec_publish(&s_done[s]);
-            }
-            // the next kept segment (its predecessor is this one)
-            uint32_t v = s + 1;
-            while (v < eff && uni(s_cut[v]) < 0) ++v;
-            if (kept && top_s == -1 && v < eff) {
-                SPEC_STAMP(v, 3, __builtin_amdgcn_s_memtime())
-                int32_t ver = 3, vfev = -1;  // (a wait that gives up: the key goes unsegmented)
-                uint32_t fev = 0;
-                if (spec_wait(&s_prdy[v]) && spec_load(&s_top[v]) != -3) {
-                    const uint32_t cut = (uint32_t)uni(s_cut[v]), end = (uint32_t)uni(s_segend[v]);
-                    const uint32_t np = uni(s_pend[v][6]);
-                    SpecState st{};
-                    spec_setup(st, lane < 6 ? s_pend[v][lane] : 0u, np, trp, ntr);
-                    // this walk's end set, relabelled from its op indices to v's
-                    const uint64_t map = uni(s_map[s]);
-                    uint32_t src = 0;
-                    for (uint32_t j = 0; j < np; ++j) {
-                        const uint32_t sl = __builtin_amdgcn_readlane(st.slot_v, j);
-                        uint32_t at = 31;
-                        for (uint32_t q = 0; q < 6; ++q)
-                            if (((map >> (8 * q)) & 0xFFu) == (0x80u | sl)) at = q;
-                        src |= ((lane >> j) & 1u) << at;
-                    }
-                    const uint32_t E = (uint32_t)__shfl((int)s_end[s][lane], (int)(src & 63u));
-                    st.W0 = lane < (1u << np) ? E : 0u;
-                    uint32_t *const sv =
-                        EX ? KA.spec_fin + ((size_t)blk * S + v) * 2 * SPEC_SAVE_WORDS + SPEC_SAVE_WORDS : nullptr;
-// (issue priority of the verifying runs: 0; 2 and 3 measured slower on
-// C2 and most seeds in round 6, profiles/r06_segments_seeds.txt)
-#ifndef LC_SPEC_VER_PRIO
-#define LC_SPEC_VER_PRIO 0
-#endif
-                    if (LC_SPEC_VER_PRIO) __builtin_amdgcn_s_setprio(LC_SPEC_VER_PRIO);
-                    const int r = spec_walk<1, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
-                                                                    s_ck[v], s_ck_e[v], 0, 0, fev, false, sv,
-                                                                    &s_done[v]);
-                    if (LC_SPEC_VER_PRIO) __builtin_amdgcn_s_setprio(0);
-                    bool last = true;
-                    for (uint32_t q = v + 1; q < eff; ++q) last = last && uni(s_cut[q]) < 0;
-                    if (r == 4) ver = 1;                        // met the TOP run
-                    else if (r == 1) { ver = 2; vfev = (int32_t)fev; }  // died before meeting it
-                    else if (r == 3) ver = 6;                   // does not fit
-                    else if (r == 5) ver = 3;                   // never met
-                    else if (last) ver = 5;                     // the last segment, searched exactly to its end
-                    else if (spec_wait(&s_done[v])) ver = (st.n <= 6 && !__any(st.W0 != s_end[v][lane])) ? 1 : 3;
-                }
-                SPEC_STAMP(v, 7, ((unsigned long long)ver << 32) | (fev - (uint32_t)uni(s_cut[v])))
-                SPEC_STAMP(v, 4, __builtin_amdgcn_s_memtime())
-                if (lane == 0) {
-                    s_ver[v] = ver;
-                    s_vfev[v] = vfev;
-                }
-            }
-        }
-    } else {
-    // 1. every segment from TOP (segment 0 exactly), from the block's queue.
-    // INVARIANT (both queue loops below): a fixed trip count (S, S - 1) and a
-    // queue index made wave-uniform by uni() before any branch on it.  With
-    // `for (;;) ... break` the compiler built an exec-masked loop whose exit
-    // hung the wave after its first walk (round 3).  tests/test_pack.py::
-    // test_spec_queue_loops_keep_fixed_trip_counts checks the shape of these
-    // loops in this file; the LC_SPEC_CHECK_UNIFORM build (make variant
-    // NAME=specchk VFLAGS=-DLC_SPEC_CHECK_UNIFORM) also checks at run time that
-    // the index is uniform, refusing the batch (LC_BATCH_E_FIT) if it is not.
+    // 1 + 2. wave w walks segment w from TOP (segment 0 exactly), then at
+    // once verifies the next kept segment from the set its own walk ended
+    // with; no barrier stands between the two.  The verifying run compares
+    // with that segment's TOP run at its checkpoints, which that run publishes
+    // as it passes them (spec_ck_event waits for one not reached yet), and
+    // with its end set once it has ended.  A block takes about its slowest
+    // TOP walk, not its slowest TOP walk plus its slowest verifying run.
+    // INVARIANT: no open loop (`for (;;) ... break` compiles into an
+    // exec-masked loop whose exit can hang the wave), and every branch on a
+    // segment index or an LDS flag is on a uni() value; the flag waits
+    // (spec_wait, spec_ck_event) have a fixed trip count.
+    // tests/test_kernel_lint.py checks these shapes in this file.
     if (!plain) {
-#pragma unroll 1
-        for (uint32_t k = 0; k < (uint32_t)S; ++k) {
-            uint32_t s = 0;
-            if (lane == 0) s = (uint32_t)atomicAdd(&s_next[0], 1);
-            s = uni(s);
-            SPEC_CHECK_UNIFORM(s);
-            if (s >= eff || uni(s_cut[s]) < 0) continue;
+        const uint32_t s = wv;
+        const bool kept = s < eff && uni(s_cut[s]) >= 0;
+        int32_t top_s = -1;
+        if (kept) {
             const int32_t cut_i = uni(s_cut[s]);
             const uint32_t cut = (uint32_t)cut_i, end = (uint32_t)uni(s_segend[s]);
             const uint32_t n0 = s == 0 ? 0u : (uint32_t)uni(s_ncand[s]);
@@ -2831,15 +2686,17 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
             }
             if (lane < 6) s_pend[s][lane] = words;
             if (lane == 6) s_pend[s][6] = np;
-            uint32_t fev = 0;
             // the ops found pending must be as many as the count says (else
             // the event stream is malformed): the key is searched unsegmented
             const bool lost = s != 0 && np != n0;
+            if (lost && lane == 0) s_top[s] = -3;
+            spec_publish(&s_prdy[s]);
+            uint32_t fev = 0;
             uint32_t *const sv = EX ? KA.spec_fin + ((size_t)blk * S + s) * 2 * SPEC_SAVE_WORDS : nullptr;
             const int r = lost ? 6
                                : spec_walk<0, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
-                                                                   s_ck[s], s_ck_e[s], KA.spec_ck1, KA.spec_ck2, fev,
-                                                                   !(KA.flags & T0_SPEC_NOPRIO), sv);
+                                                                   s_ck[s], s_ck_e[s], KA.spec_ck1, KA.spec_ck2,
+                                                                   fev, !(KA.flags & T0_SPEC_NOPRIO), sv);
             s_end[s][lane] = st.W0;
             uint64_t map = 0;
             for (uint32_t q = 0; q < 6; ++q) {
@@ -2847,34 +2704,27 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
                 if ((st.live >> q) & 1u) map |= (uint64_t)(0x80u | sl) << (8 * q);
             }
             SPEC_STAMP(s, 2, __builtin_amdgcn_s_memtime())
+            top_s = r == 1 ? (int32_t)fev : r == 3 ? -2 : r == 6 ? -3 : -1;
             if (lane == 0) {
                 s_map[s] = map;
-                s_top[s] = r == 1 ? (int32_t)fev : r == 3 ? -2 : r == 6 ? -3 : -1;
+                s_top[s] = top_s;
             }
+            spec_publish(&s_done[s]);
         }
-    }
-    __syncthreads();
-    // 2. every segment s >= 1 again, from the set segment s - 1 ended with,
-    // until the runs meet (from the block's second queue)
-    if (!plain) {
-#pragma unroll 1
-        for (uint32_t k = 1; k < (uint32_t)S; ++k) {
-            uint32_t s = 0;
-            if (lane == 0) s = (uint32_t)atomicAdd(&s_next[1], 1) + 1u;
-            s = uni(s);
-            SPEC_CHECK_UNIFORM(s);
-            if (s >= eff || uni(s_cut[s]) < 0 || uni(s_top[s]) == -3) continue;
-            SPEC_STAMP(s, 3, __builtin_amdgcn_s_memtime())
-            uint32_t pw = s - 1;
-            while (uni(s_cut[pw]) < 0) --pw;  // s_cut[0] = 0
-            int32_t ver = 0, vfev = -1;
-            if (uni(s_top[pw]) == -1) {
-                const uint32_t cut = (uint32_t)uni(s_cut[s]), end = (uint32_t)uni(s_segend[s]);
-                const uint32_t np = uni(s_pend[s][6]);
+        // the next kept segment (its predecessor is this one)
+        uint32_t v = s + 1;
+        while (v < eff && uni(s_cut[v]) < 0) ++v;
+        if (kept && top_s == -1 && v < eff) {
+            SPEC_STAMP(v, 3, __builtin_amdgcn_s_memtime())
+            int32_t ver = 3, vfev = -1;  // (a wait that gives up: the key goes unsegmented)
+            uint32_t fev = 0;
+            if (spec_wait(&s_prdy[v]) && spec_load(&s_top[v]) != -3) {
+                const uint32_t cut = (uint32_t)uni(s_cut[v]), end = (uint32_t)uni(s_segend[v]);
+                const uint32_t np = uni(s_pend[v][6]);
                 SpecState st{};
-                spec_setup(st, lane < 6 ? s_pend[s][lane] : 0u, np, trp, ntr);
-                // the predecessor's end set, relabelled from its op indices to these
-                const uint64_t map = uni(s_map[pw]);
+                spec_setup(st, lane < 6 ? s_pend[v][lane] : 0u, np, trp, ntr);
+                // this walk's end set, relabelled from its op indices to v's
+                const uint64_t map = uni(s_map[s]);
                 uint32_t src = 0;
                 for (uint32_t j = 0; j < np; ++j) {
                     const uint32_t sl = __builtin_amdgcn_readlane(st.slot_v, j);
@@ -2883,32 +2733,32 @@ __global__ __launch_bounds__(64 * W, (W == 2 ? LC_SPEC2_WAVES : W == 8 ? LC_SPEC
                         if (((map >> (8 * q)) & 0xFFu) == (0x80u | sl)) at = q;
                     src |= ((lane >> j) & 1u) << at;
                 }
-                const uint32_t E = (uint32_t)__shfl((int)s_end[pw][lane], (int)(src & 63u));
+                const uint32_t E = (uint32_t)__shfl((int)s_end[s][lane], (int)(src & 63u));
                 st.W0 = lane < (1u << np) ? E : 0u;
-                uint32_t fev = 0;
                 uint32_t *const sv =
-                    EX ? KA.spec_fin + ((size_t)blk * S + s) * 2 * SPEC_SAVE_WORDS + SPEC_SAVE_WORDS : nullptr;
-                // (the verifying runs at a TOP walk's highest issue priority,
-                // against the other blocks' TOP walks on the SIMD, measured
-                // slower in round 5: C2 0.2484 -> 0.2501, C5 0.2997 -> 0.3068)
+                    EX ? KA.spec_fin + ((size_t)blk * S + v) * 2 * SPEC_SAVE_WORDS + SPEC_SAVE_WORDS : nullptr;
+                // (the verifying runs stay at issue priority 0: 2 and 3 measured
+                // slower on C2 and most seeds, profiles/r06_segments_seeds.txt)
                 const int r = spec_walk<1, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
-                                                                s_ck[s], s_ck_e[s], 0, 0, fev, false, sv);
+                                                                s_ck[v], s_ck_e[v], 0, 0, fev, false, sv,
+                                                                &s_done[v]);
                 bool last = true;
-                for (uint32_t q = s + 1; q < eff; ++q) last = last && uni(s_cut[q]) < 0;
+                for (uint32_t q = v + 1; q < eff; ++q) last = last && uni(s_cut[q]) < 0;
                 if (r == 4) ver = 1;                        // met the TOP run
                 else if (r == 1) { ver = 2; vfev = (int32_t)fev; }  // died before meeting it
                 else if (r == 3) ver = 6;                   // does not fit
                 else if (r == 5) ver = 3;                   // never met
                 else if (last) ver = 5;                     // the last segment, searched exactly to its end
-                else ver = (st.n <= 6 && !__any(st.W0 != s_end[s][lane])) ? 1 : 3;
-                SPEC_STAMP(s, 7, ((unsigned long long)ver << 32) | (fev - cut))
+                else if (spec_wait(&s_done[v])) ver = (st.n <= 6 && !__any(st.W0 != s_end[v][lane])) ? 1 : 3;
             }
-            SPEC_STAMP(s, 4, __builtin_amdgcn_s_memtime())
-            if (lane == 0) { s_ver[s] = ver; s_vfev[s] = vfev; }
+            SPEC_STAMP(v, 7, ((unsigned long long)ver << 32) | (fev - (uint32_t)uni(s_cut[v])))
+            SPEC_STAMP(v, 4, __builtin_amdgcn_s_memtime())
+            if (lane == 0) {
+                s_ver[v] = ver;
+                s_vfev[v] = vfev;
+            }
         }
     }
-    }  // LC_SPEC_OVERLAP
-    if (LC_SPEC_CUT_PRIO) __builtin_amdgcn_s_setprio(0);
     __syncthreads();
     if (wv == 0) {
         for (uint32_t s = 0; s < (uint32_t)S; ++s) { SPEC_STAMP(s, 5, __builtin_amdgcn_s_memtime()) }
@@ -3005,7 +2855,7 @@ size_t spec_ws_words(int64_t n_keys, int segs) { return (size_t)std::max<int64_t
 size_t spec_fin_words(int64_t n_keys, int segs) {
     return (size_t)std::max<int64_t>(n_keys, 1) * segs * 2 * SPEC_SAVE_WORDS;
 }
-hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, int waves, uint32_t *ws, int32_t *rr, int parity,
+hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, uint32_t *ws, int32_t *rr, int parity,
                        uint32_t ck1, uint32_t ck2, int rerun_grid, int validate_blocks, const uint16_t *events16,
                        bool cost_cuts, bool prio, bool vfirst, uint32_t *fin, bool stage, hipStream_t s) {
     T0Args t = make_t0(a, a_dev);
@@ -3025,18 +2875,17 @@ hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, int waves, ui
     const dim3 rgrid((unsigned)std::max(1, std::min((a.n_order + SPEC_RERUN_WAVES - 1) / SPEC_RERUN_WAVES, rerun_grid)));
     // one wave per segment: more segments than waves (8, 12 or 16 on 4
     // waves, 4 or 8 on 2) measured slower (device_api.hip)
-    (void)waves;
-#define LC_SPEC_L(SS, WW, E, X) hipLaunchKernelGGL((k_spec<SS, WW, E, X>), grid, dim3(64 * WW), 0, s, t)
-#define LC_SPEC_ALL(E)                                                   \
-    if (fin) {                                                           \
-        if (segs >= 8) LC_SPEC_L(8, 8, E, true);                         \
-        else if (segs >= 4) LC_SPEC_L(4, 4, E, true);                    \
-        else LC_SPEC_L(2, 2, E, true);                                   \
-    } else if (segs >= 8) LC_SPEC_L(8, 8, E, false);                    \
-    else if (segs >= 6) LC_SPEC_L(6, 6, E, false);                       \
-    else if (segs >= 4) LC_SPEC_L(4, 4, E, false);                       \
-    else if (segs >= 3) LC_SPEC_L(3, 3, E, false);                       \
-    else LC_SPEC_L(2, 2, E, false);
+#define LC_SPEC_L(SS, E, X) hipLaunchKernelGGL((k_spec<SS, E, X>), grid, dim3(64 * SS), 0, s, t)
+#define LC_SPEC_ALL(E)                                      \
+    if (fin) {                                              \
+        if (segs >= 8) LC_SPEC_L(8, E, true);               \
+        else if (segs >= 4) LC_SPEC_L(4, E, true);          \
+        else LC_SPEC_L(2, E, true);                         \
+    } else if (segs >= 8) LC_SPEC_L(8, E, false);           \
+    else if (segs >= 6) LC_SPEC_L(6, E, false);             \
+    else if (segs >= 4) LC_SPEC_L(4, E, false);             \
+    else if (segs >= 3) LC_SPEC_L(3, E, false);             \
+    else LC_SPEC_L(2, E, false);
     if (events16) { LC_SPEC_ALL(true) } else { LC_SPEC_ALL(false) }
 #undef LC_SPEC_ALL
 #undef LC_SPEC_L

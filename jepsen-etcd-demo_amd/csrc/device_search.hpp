@@ -70,7 +70,7 @@ constexpr int32_t LC_BATCH_E_FIT = 4;    // a key declared to fit T0 (width, sta
 // Ops pending at once above which a key leaving T0 goes straight to T3.
 constexpr uint32_t LC_DIRECT_T3_WIDTH = 28;
 
-// The speculative segments' 8-wave build (k_spec<8, 8>, device_lattice.hip)
+// The speculative segments' 8-wave build (k_spec<8>, device_lattice.hip)
 // held to 8 waves per SIMD -- 64 VGPRs, the rest spilled -- so a batch of up
 // to 1,024 keys (C2, C5) has all 8 walks of every key resident at once: the
 // launch chooses 8 segments per key there instead of 4 (round 5, C2
@@ -143,7 +143,7 @@ size_t spec_ws_words(int64_t n_keys, int segs);
 // event counts;
 // prio: TOP walks' issue priority by progress (s_setprio).
 size_t spec_fin_words(int64_t n_keys, int segs);
-hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, int waves, uint32_t *ws, int32_t *rr, int parity,
+hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, uint32_t *ws, int32_t *rr, int parity,
                        uint32_t ck1, uint32_t ck2, int rerun_grid, int validate_blocks, const uint16_t *events16,
                        bool cost_cuts, bool prio, bool vfirst, uint32_t *fin, bool stage, hipStream_t s);
 uint32_t t0_max_width();   // most ops pending at once that T0 holds

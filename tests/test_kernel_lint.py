@@ -2,7 +2,8 @@
 
 Round 3: a `for (;;) ... break` walk loop in k_spec (device_lattice.hip) was
 compiled into an exec-masked loop whose exit hung the wave after its first
-walk; it was replaced by fixed trip counts over uni()-uniform queue indices.
+walk; it was replaced by fixed trip counts over uni()-uniform values.  The
+kernel's LDS-flag waits (spec_wait, spec_ck_event) are loops of the same kind.
 No run-time test can see a future edit that undoes that (the hang only
 shows on the GPU), so the loop shapes are checked here, in the source."""
 import os
@@ -29,18 +30,49 @@ def _code(text: str) -> str:
     return "\n".join(line.split("//")[0] for line in text.splitlines())
 
 
-def test_spec_queue_loops_keep_fixed_trip_counts():
-    src = open(os.path.join(CSRC, "device_lattice.hip")).read()
-    head = re.search(r"__global__ __launch_bounds__\(64 \* W[^)]*\)\) void k_spec\(", src)
+OPEN_LOOP = r"for\s*\(\s*;\s*;\s*\)|while\s*\(\s*(true|1)\s*\)"
+
+
+def test_spec_walks_and_flag_waits_keep_fixed_trip_counts():
+    src = _code(open(os.path.join(CSRC, "device_lattice.hip")).read())
+    head = re.search(r"__global__ __launch_bounds__\([^{;]*\) void k_spec\(", src)
     assert head, "k_spec's definition not found"
-    body = _code(_body(src, head.group(0)))
-    assert not re.search(r"for\s*\(\s*;\s*;\s*\)|while\s*\(\s*(true|1)\s*\)", body), "an open loop in k_spec"
-    for start, queue in (("0", "s_next[0]"), ("1", "s_next[1]")):
-        m = re.search(r"for \(uint32_t k = %s; k < \(uint32_t\)S; \+\+k\) \{(.{0,400})" % start, body, re.S)
-        assert m, f"k_spec's queue loop from {start} lost its fixed trip count"
-        head = m.group(1)
-        assert queue in head and "s = uni(s);" in head, f"queue index of loop {start} not made uniform by uni()"
-        assert "SPEC_CHECK_UNIFORM(s);" in head
+    k_spec = _body(src, head.group(0))
+    bodies = {"k_spec": k_spec}
+    for name, ret in (("spec_walk", "int"), ("spec_wait", "bool"), ("spec_ck_event", "int32_t")):
+        bodies[name] = _body(src, f"__device__ __forceinline__ {ret} {name}(")
+    for name, body in bodies.items():
+        assert not re.search(OPEN_LOOP, body), f"an open loop in {name}"
+
+    # the LDS-flag waits: a fixed trip count, every flag read a spec_load
+    for name, flags in (("spec_wait", ("f",)), ("spec_ck_event", ("ck_e", "top_done"))):
+        body = bodies[name]
+        assert len(re.findall(r"\b(for|while|do)\b", body)) == 1, f"{name} has more than its one wait loop"
+        at = re.search(r"for \(uint32_t it = 0; it < SPEC_WAIT_MAX; \+\+it\) ", body)
+        assert at, f"{name}'s wait lost its fixed trip count"
+        loop = _body(body[at.start():], at.group(0))
+        rest, n_loads = re.subn(r"\bspec_load\([^()]*\)", "", loop)
+        assert n_loads >= 1, f"{name} polls no flag"
+        assert "__hip_atomic_load" not in rest
+        for flag in flags:
+            assert not re.search(r"\b%s\b" % flag, rest), f"{name} reads {flag} without spec_load"
+    load = _body(src, "__device__ __forceinline__ int32_t spec_load(")
+    assert re.search(r"\{\s*return uni\(__hip_atomic_load\(f, __ATOMIC_ACQUIRE, [^;]*\)\);\s*\}$", load), \
+        "spec_load is no longer a uni() of an acquire load"
+
+    # k_spec's walks: the wave's segment index and the scan for the next kept
+    # segment branch on wave-uniform values only
+    assert re.search(r"\bwv = uni\(\(uint32_t\)threadIdx\.x >> 6\)", k_spec), "the wave index is not made uniform"
+    at = k_spec.index("const uint32_t s = wv;")
+    start = k_spec.rindex("if (!plain) {", 0, at)
+    assert not k_spec[start + len("if (!plain) {"):at].strip(), "the walks' block does not start at its segment index"
+    walks = _body(k_spec[start:], "if (!plain) ")
+    assert "const bool kept = s < eff && uni(s_cut[s]) >= 0;" in walks
+    assert "while (v < eff && uni(s_cut[v]) < 0) ++v;" in walks
+    uses = [m.start() for m in re.finditer(r"s_cut\[", walks)]
+    assert len(uses) >= 2
+    for u in uses:
+        assert walks[:u].endswith("uni("), "s_cut read without uni(): " + walks[u:u + 40]
 
 
 def test_wgl_work_loop_is_bounded():

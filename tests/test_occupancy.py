@@ -58,9 +58,9 @@ def _waves_per_simd(k):
 
 
 @pytest.mark.parametrize("name,want", [
-    ("_ZN3lcd6k_specILi8ELi8ELb1ELb0EEEvNS_6T0ArgsE", 8),  # C2/C5-sized batches: 8 segments, all resident
-    ("_ZN3lcd6k_specILi2ELi2ELb1ELb0EEEvNS_6T0ArgsE", 8),  # the many-key batches (C3 shards)
-    ("_ZN3lcd6k_specILi4ELi4ELb1ELb0EEEvNS_6T0ArgsE", 4),
+    ("_ZN3lcd6k_specILi8ELb1ELb0EEEvNS_6T0ArgsE", 8),  # C2/C5-sized batches: 8 segments, all resident
+    ("_ZN3lcd6k_specILi2ELb1ELb0EEEvNS_6T0ArgsE", 8),  # the many-key batches (C3 shards)
+    ("_ZN3lcd6k_specILi4ELb1ELb0EEEvNS_6T0ArgsE", 4),
 ])
 def test_spec_builds_keep_their_occupancy(tmp_path, name, want):
     ks = _kernels(tmp_path)
@@ -71,9 +71,9 @@ def test_spec_builds_keep_their_occupancy(tmp_path, name, want):
 
 
 @pytest.mark.parametrize("name", [
-    "_ZN3lcd6k_specILi8ELi8ELb1ELb0EEEvNS_6T0ArgsE",  # C2 / C5 (verdict records)
-    "_ZN3lcd6k_specILi2ELi2ELb1ELb0EEEvNS_6T0ArgsE",  # the C3 shards
-    "_ZN3lcd6k_specILi4ELi4ELb1ELb0EEEvNS_6T0ArgsE",
+    "_ZN3lcd6k_specILi8ELb1ELb0EEEvNS_6T0ArgsE",  # C2 / C5 (verdict records)
+    "_ZN3lcd6k_specILi2ELb1ELb0EEEvNS_6T0ArgsE",  # the C3 shards
+    "_ZN3lcd6k_specILi4ELb1ELb0EEEvNS_6T0ArgsE",
 ])
 def test_spec_builds_do_not_spill(tmp_path, name):
     """the 64-VGPR builds held their occupancy by spilling

@@ -1,5 +1,5 @@
 """Final configs without peaks (the Jepsen-shaped checkers: exact speculative
-segments, k_spec<S, S, E16, EX>): segments per key 4 (the default for such
+segments, k_spec<S, E16, EX>): segments per key 4 (the default for such
 batches) against 8, device time per batch (lc_stats.kernel_ms), records
 (verdicts, failing events, final-config records) required equal.
 usage: python tools/ex_segs_ab.py"""
