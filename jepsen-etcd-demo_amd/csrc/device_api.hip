@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "device_search.hpp"
+#include "step_plan.hpp"
 
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
@@ -38,7 +39,14 @@
             return lc::fail(LC_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));  \
     } while (0)
 
-#define RCCLCHK(expr)                                                                      \
+// a step of ours that failed: its code goes up as it is (lc::fail has the message)
+#define LCCHK(expr)            \
+    do {                       \
+        int _rc = (expr);      \
+        if (_rc) return _rc;   \
+    } while (0)
+
+#define RCCLCHK(expr)                                                                     \
     do {                                                                                   \
         ncclResult_t _r = (expr);                                                          \
         if (_r != ncclSuccess)                                                             \
@@ -124,17 +132,6 @@ __global__ void k_take_err(int32_t *words, uint32_t mask, int32_t *out) {
         const bool on = (mask >> q) & 1u;
         out[2 * q] = on ? atomicExch(&words[2 * q], 0) : 0;
         out[2 * q + 1] = on ? atomicExch(&words[2 * q + 1], 0) : 0;
-    }
-}
-
-// Verdict record of one key (include/lincheck.h LC_REC_*), 0 for padding.
-__global__ void k_pack_records(const int8_t *valid, const uint8_t *cause, const int32_t *fail_event, int64_t n,
-                               int64_t block, uint64_t *out) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < block; i += (int64_t)gridDim.x * blockDim.x) {
-        uint64_t r = 0;
-        if (i < n)
-            r = (uint64_t)(uint8_t)(valid[i] + 1) | (uint64_t)cause[i] << 8 | (uint64_t)(uint32_t)(fail_event[i] + 1) << 16;
-        out[i] = r;
     }
 }
 
@@ -1190,39 +1187,51 @@ static int run_wgl(Dev *c, const DevBatch *d, const lcd::Args &a, const int32_t 
 
 enum ResMode { RES_HOST = 0, RES_DEV = 1, RES_CTX = 2 };
 
-// Search d on c.  RES_HOST: r's arrays are host memory and receive the
-// results; RES_DEV: r's arrays are device memory on c; RES_CTX: results stay
-// in c's own device arrays (r unused).  allow_async: a step that is T0 alone
-// is only enqueued (*enqueued = true; errors surface at the next wait).
-// k_spec_rerun's workgroups at most (0: one per CU; A/B: make variant
-// VFLAGS=-DLC_SPEC_RERUN_BLOCKS=n -- 16 and 64 measured the same as 256 on
-// C2 in round 5, 0.2552-0.2556 ms per step)
-#ifndef LC_SPEC_RERUN_BLOCKS
-#define LC_SPEC_RERUN_BLOCKS 0
-#endif
-static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mode, bool allow_async, int64_t key0,
-                      lc_stats *st, bool *enqueued = nullptr, int64_t res_off = 0) {
-    lc::Range range("lincheck: search");
-    if (enqueued) *enqueued = false;
-    auto t0 = std::chrono::steady_clock::now();
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t K = d->n_keys;
-    if (K > 0x7FFFFFFF) return lc::fail(LC_E_INVALID, "lc_check_device: too many keys");
-    int rc = ensure_capacity(c, K);
-    if (rc) return rc;
-    const lc_opts &o = *c->o;
-
+// One search step, as dev_search's stages see it: where it runs, its plan
+// (step_plan.hpp), the Args every launch of it shares, and what the tiers
+// leave for fill_stats.
+struct Step {
+    Dev *c;
+    const DevBatch *d;
+    const lc_result *r;
+    ResMode mode;
+    int64_t K;
+    std::chrono::steady_clock::time_point t0;
+    lc::StepPlan p;
     lcd::Args a{};
+    uint8_t *analyzer = nullptr;  // which analysis answered each key (lc_result.analyzer), or null
+    uint32_t ticket_base = 0;
+    bool t3 = false;
+    unsigned long long probes_pre_t3 = 0;
+    int32_t n_deep = 0, n_widek = 0;
+    float ms = 0, ms0 = 0, ms3 = 0, msw = 0;
+    uint64_t wgl_keys = 0, wgl_steps = 0, wgl_spilled = 0;
+};
+
+// The work lists between the tiers (Dev::lists) and their counts (Dev::counters).
+struct Lists {
+    int32_t *spill0, *spill1, *spill2, *wide, *old_narrow;
+    int32_t *n_spill0, *n_spill1, *n_spill2, *n_wide;
+};
+static Lists lists_of(const Dev *c) {
+    return {c->lists, c->lists + c->cap_keys, c->lists + 2 * c->cap_keys, c->lists + 3 * c->cap_keys,
+            c->lists + 4 * c->cap_keys, c->counters + 0, c->counters + 1, c->counters + 2, c->counters + 3};
+}
+
+// The Args every launch of the step shares (strict and, for an enqueued
+// step, err follow the plan), and the step's analyzer array.
+static void step_args(Step &s, int64_t key0, int64_t res_off) {
+    Dev *c = s.c;
+    const DevBatch *d = s.d;
+    const lc_result *r = s.r;
+    const ResMode mode = s.mode;
+    const lc_opts &o = *c->o;
+    lcd::Args &a = s.a;
     a.ev_off = d->ev_off; a.events = d->events; a.trans = d->trans; a.trans_off = d->trans_off;
     a.key_width = d->key_width; a.key_states = d->key_states; a.key_error = d->key_error;
     a.table = d->table;
     a.init_state = d->init_state; a.shared_states = d->shared_states;
     a.n_trans = (uint32_t)d->n_trans;
-    // T0_STRICT: a register-tier batch the host did not walk (T0 refuses a key
-    // that does not fit instead of spilling it); other unwalked batches get
-    // the general validation kernel ahead of the set tiers
-    a.strict = (!d->validated && d->t0_only) ? 1 : 0;
-    const bool gen_validate = !d->validated && !d->t0_only;
     a.budget = o.max_configs; a.max_final = o.max_final; a.debug_mode = o.debug_mode;
     a.count_probes = (o.flags & LC_OPT_COUNT_PROBES) ? 1 : 0;
     if (mode == RES_DEV) {
@@ -1239,210 +1248,157 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
     a.err = c->counters + 4;
     a.err_base = (int32_t)key0;  // malformed keys are reported by their index in the caller's batch
     a.list_cap = (int32_t)c->cap_keys;
-    // which analysis answered each key (lc_result.analyzer)
-    uint8_t *const analyzer = mode == RES_DEV ? r->analyzer : (mode == RES_HOST && r->analyzer) ? c->analyzer : nullptr;
-    if (analyzer && K > 0 && o.algorithm != LC_ALGO_WGL)
-        HIPCHK(hipMemsetAsync(analyzer, LC_ALGO_LINEAR, (size_t)K, c->stream));
-    if (o.algorithm == LC_ALGO_WGL) {
-        // knossos.wgl's own search (device_wgl.hip) for every key
-        if (enqueued) *enqueued = false;
-        HIPCHK(hipMemsetAsync(c->ctl, 0, 4 * sizeof(unsigned long long) + 4 * sizeof(int32_t), c->stream));
-        HIPCHK(hipMemsetAsync(c->counters + 6, 0, 10 * sizeof(int32_t), c->stream));
-        c->ticket_live = false;
-        if (!d->ev32_ready && d->n_events) {
-            const uint64_t n4 = (d->n_events + 3) / 4;
-            const int blocks = (int)std::min<uint64_t>((n4 + 255) / 256, (uint64_t)c->cu_count * 8);
-            hipLaunchKernelGGL(k_widen16, dim3(std::max(blocks, 1)), dim3(256), 0, c->stream, d->events16, d->events,
-                               d->n_events);
-            HIPCHK(hipGetLastError());
-            d->ev32_ready = true;
-        }
-        if (a.n_final && K > 0) HIPCHK(hipMemsetAsync(a.n_final, 0, (size_t)K * 4, c->stream));
-        HIPCHK(hipEventRecord(c->e0, c->stream));
-        if (!d->validated && K > 0) {  // the per-event checks the host skipped, ahead of the walk
-            lcd::Args av = a;
-            av.n_order = (int32_t)K;
-            HIPCHK(lcd::launch_validate(av, c->stream, true));
-        }
-        lc_stats ws{};
-        rc = run_wgl(c, d, a, d->order, (int32_t)K, nullptr, K, analyzer, &ws);
-        if (rc) return rc;
-        HIPCHK(hipEventRecord(c->e1, c->stream));
-        HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
-        if (mode == RES_HOST && K > 0) {
-            HIPCHK(hipMemcpyAsync(r->valid, c->valid, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(r->fail_event, c->fail_event, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(r->cause, c->cause, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            if (r->peak_configs)
-                HIPCHK(hipMemcpyAsync(r->peak_configs, c->peak, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            if (r->final_configs)
-                HIPCHK(hipMemcpyAsync(r->final_configs, c->final_cfg, (size_t)K * o.max_final * 16,
-                                      hipMemcpyDeviceToHost, c->stream));
-            if (r->n_final)
-                HIPCHK(hipMemcpyAsync(r->n_final, c->n_final, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            if (r->analyzer)
-                HIPCHK(hipMemcpyAsync(r->analyzer, c->analyzer, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        rc = take_error(c);
-        if (rc) return rc;
-        float ms = 0, msw = 0;
-        HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-        if (K > 0) HIPCHK(hipEventElapsedTime(&msw, c->et3a, c->et3b));
-        if (st) {
-            *st = lc_stats{};
-            st->kernel_ms = ms;
-            st->wgl_ms = msw;
-            st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-            st->lds_keys = c->hctl[2];
-            st->wgl_keys = c->hctl[2];
-            st->wgl_steps = c->hctl[1];
-            st->events = c->hctl[1];
-            st->probes = c->hctl[0];  // Lowe's cache lookups
-            st->wgl_spilled = ws.wgl_spilled;
-        }
-        return LC_OK;
-    }
-    const bool competition = o.algorithm == LC_ALGO_COMPETITION;
-    if (competition) allow_async = false;  // the WGL step needs the :linear step's causes
-    int32_t *spill0 = c->lists, *spill1 = c->lists + c->cap_keys, *spill2 = c->lists + 2 * c->cap_keys;
-    int32_t *wide = c->lists + 3 * c->cap_keys, *old_narrow = c->lists + 4 * c->cap_keys;
-    int32_t *n_spill0 = c->counters + 0, *n_spill1 = c->counters + 1, *n_spill2 = c->counters + 2;
-    int32_t *n_wide = c->counters + 3;
+    s.analyzer = mode == RES_DEV ? r->analyzer : (mode == RES_HOST && r->analyzer) ? c->analyzer : nullptr;
+}
 
-    // Nothing counted and no key can leave T0: no T1/T2 launches, no counter
-    // readback and no control-block memset -- the step is T0 alone (plus the
-    // result download when the results go to host memory).
-    const bool t0_step = K > 0 && d->t0_only && !(o.flags & LC_OPT_COUNT_PROBES);
-    const bool async = t0_step && allow_async && mode != RES_HOST;
-    if (!async && c->ea1_pending) {  // the asynchronous steps' span ends before this one
-        HIPCHK(hipEventRecord(c->ea1, c->stream));
-        c->ea1_pending = false;
+// What plan_step decides from: the batch, the options, what s.a asks for.
+static lc::StepIn step_in(const Step &s, bool allow_async) {
+    const DevBatch *d = s.d;
+    const lc_opts &o = *s.c->o;
+    lc::StepIn in;
+    in.K = s.K; in.n_events = d->n_events; in.cu_count = s.c->cu_count;
+    in.t0_only = d->t0_only; in.table = d->table != nullptr; in.taggable = d->taggable; in.seg_pays = d->seg_pays;
+    in.validated = d->validated; in.has_events16 = d->events16 != nullptr;
+    in.algorithm = o.algorithm; in.flags = o.flags; in.path_flags = o.path_flags; in.spec_segs = o.spec_segs;
+    in.max_configs = o.max_configs;
+    in.want_peak = s.a.peak != nullptr; in.want_final = s.a.final_cfg != nullptr; in.want_n_final = s.a.n_final != nullptr;
+    in.res_host = s.mode == RES_HOST; in.allow_async = allow_async;
+    in.spec8_waves = LC_SPEC8_WAVES;
+    in.ws_words = lcd::spec_ws_words(1, 1); in.fin_words = lcd::spec_fin_words(1, 1);
+    in.ws_max_bytes = SPEC_WS_MAX_BYTES;
+    return in;
+}
+
+// The 32-bit event words every kernel but k_spec reads, widened once per
+// upload from a batch's 16-bit ones.
+static int ensure_ev32(Dev *c, const DevBatch *d) {
+    if (d->ev32_ready || !d->n_events) return LC_OK;
+    const uint64_t n4 = (d->n_events + 3) / 4;
+    const int blocks = (int)std::min<uint64_t>((n4 + 255) / 256, (uint64_t)c->cu_count * 8);
+    hipLaunchKernelGGL(k_widen16, dim3(std::max(blocks, 1)), dim3(256), 0, c->stream, d->events16, d->events,
+                       d->n_events);
+    HIPCHK(hipGetLastError());
+    d->ev32_ready = true;
+    return LC_OK;
+}
+
+// Zero the control block: everything but the error words (a malformed batch
+// reported at the next wait keeps them until then).
+static int zero_control(Dev *c) {
+    HIPCHK(hipMemsetAsync(c->ctl, 0, 4 * sizeof(unsigned long long) + 4 * sizeof(int32_t), c->stream));
+    HIPCHK(hipMemsetAsync(c->counters + 6, 0, 10 * sizeof(int32_t), c->stream));
+    return LC_OK;
+}
+
+// The control block, and with RES_HOST the results, to the host; then the
+// stream's end and the step's error words.
+static int readback(const Step &s) {
+    Dev *c = s.c;
+    const lc_result *r = s.r;
+    const size_t K = (size_t)s.K;
+    HIPCHK(hipEventRecord(c->e1, c->stream));
+    HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
+    if (s.mode == RES_HOST && K > 0) {
+        HIPCHK(hipMemcpyAsync(r->valid, c->valid, K, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(r->fail_event, c->fail_event, K * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(r->cause, c->cause, K, hipMemcpyDeviceToHost, c->stream));
+        if (r->peak_configs) HIPCHK(hipMemcpyAsync(r->peak_configs, c->peak, K * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r->final_configs)
+            HIPCHK(hipMemcpyAsync(r->final_configs, c->final_cfg, K * c->o->max_final * 16, hipMemcpyDeviceToHost,
+                                  c->stream));
+        if (r->n_final) HIPCHK(hipMemcpyAsync(r->n_final, c->n_final, K * 4, hipMemcpyDeviceToHost, c->stream));
+        if (r->analyzer) HIPCHK(hipMemcpyAsync(r->analyzer, c->analyzer, K, hipMemcpyDeviceToHost, c->stream));
     }
-    // an enqueued step reports a malformed batch through its own error words
-    if (async) a.err = c->counters + ERR_RING + 2 * (int)(c->async_seq % 4);
-    // Key segments (device_lattice.hip): verdicts only, a batch of about one
-    // key per SIMD or fewer (where each key's serial chain is exposed), and
-    // quiescent points close enough for the cuts to pay (segments_pay: on
-    // C2, whose clients think about as long as an op takes, the longest
-    // stretch without one is most of a key, so its keys stay whole).
-    // lc_opts.path_flags LC_PATH_SPLIT_ON / _OFF pin the choice (A/B and tests).
-    const bool fast = !a.peak && !a.final_cfg && o.max_configs >= 16ull * 64 * 32;
-    const bool want = (o.path_flags & LC_PATH_SPLIT_ON) ? true : (o.path_flags & LC_PATH_SPLIT_OFF) ? false : d->seg_pays;
-    const bool split = t0_step && fast && d->taggable && want && K <= (int64_t)c->cu_count * 8;
-    if (split) {
-        rc = ensure_segments(c, K);
-        if (rc) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return take_error(c);
+}
+
+// The :wgl-only step: knossos.wgl's own search (device_wgl.hip) for every key.
+static int search_wgl(Step &s, lc_stats *st) {
+    Dev *c = s.c;
+    const DevBatch *d = s.d;
+    const int64_t K = s.K;
+    LCCHK(zero_control(c));
+    c->ticket_live = false;
+    LCCHK(ensure_ev32(c, d));
+    if (s.a.n_final && K > 0) HIPCHK(hipMemsetAsync(s.a.n_final, 0, (size_t)K * 4, c->stream));
+    HIPCHK(hipEventRecord(c->e0, c->stream));
+    if (!d->validated && K > 0) {  // the per-event checks the host skipped, ahead of the walk
+        lcd::Args av = s.a;
+        av.n_order = (int32_t)K;
+        HIPCHK(lcd::launch_validate(av, c->stream, true));
     }
-    // Speculative segments (device_lattice.hip): the same regime without
-    // quiescent points -- every key a workgroup of `segs` waves, about four
-    // segment waves per SIMD in all (C2: 1,000 keys x 4).  The kernel's 80
-    // VGPRs would allow six, but 6-wave workgroups land unevenly on a CU's
-    // four SIMDs (5-7 waves each): C2 0.357 ms at 4 segments per key, 0.406
-    // at 6, 0.386 at 8.  lc_opts: LC_PATH_SPEC_OFF turns them off, spec_segs
-    // pins the segments per key.
-    //
-    // Large batches too (C3 shards: 2 segments per key; 12,500 x 2,000 4.44
-    // ms against 5.51 unsegmented, the whole C3 key space 33.2 against 38.0).
-    // More segments than waves (a key's waves taking its segments from a
-    // block-local queue) measured slower: C2 8 segments on 4 waves
-    // 0.302 ms, 12 on 4 0.332, against 0.273 for 4 on 4; a C3 shard 4 on 2
-    // 4.75 ms, 8 on 2 5.30, against 4.40 for 2 on 2.
-    int segs = K > 0 ? (int)std::min<int64_t>(8, (int64_t)c->cu_count * 4 * 4 / std::max<int64_t>(K, 1)) : 0;
-    segs = segs >= 8 ? 8 : segs >= 4 ? 4 : K > 0 ? 2 : 0;
-    // Final configs wanted and no set sizes (the Jepsen-shaped checkers):
-    // the segments with exact sets (Knossos's S, not its closure), each run
-    // saving its set at its end or death, the true run's written as the
-    // key's final configs (k_spec<.., EX>).
-    const bool exact_spec = !a.peak && a.final_cfg && a.n_final && o.max_configs >= 16ull * 64 * 32;
-    // 8 per key while 8 x keys waves are resident at the 8-wave build's 8
-    // per SIMD (device_search.hpp LC_SPEC8_WAVES).  The exact segments too
-    // since round 6 (spill-free builds, overlapped verifying runs;
-    // tools/ex_segs_ab.py, records equal): C2 0.2843 -> 0.2530 ms, a C5-shaped
-    // batch of another seed 0.2822 -> 0.2627, BASELINE's C5 0.2717 -> 0.2755.
-    // (Round 5, before both: C5 0.289 -> 0.352 ms with 8.)
-    if (LC_SPEC8_WAVES >= 8 && (fast || exact_spec) && K > 0 && K * 8 <= (int64_t)c->cu_count * 4 * 8) segs = 8;
-    if (o.spec_segs) segs = o.spec_segs;
-    if (exact_spec && !fast) segs = segs >= 8 ? 8 : segs >= 4 ? 4 : 2;  // the exact builds
-    bool spec = !split && t0_step && (fast || exact_spec) && segs >= 2 && !(o.path_flags & LC_PATH_SPEC_OFF);
-    // The segments' workspaces are per key: a batch whose keys
-    // would need more than SPEC_WS_MAX_BYTES of them takes the unsegmented
-    // register tier, whose workspace is per resident wave.
-    if (spec && (uint64_t)(lcd::spec_ws_words(K, segs) + (exact_spec && !fast ? lcd::spec_fin_words(K, segs) : 0)) * 4 >
-                    SPEC_WS_MAX_BYTES)
-        spec = false;
-    if (spec) {
-        const size_t need = lcd::spec_ws_words(K, segs);
-        if (need > c->spec_ws_words) {
-            if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
-            dfree(c->spec_ws);
-            c->spec_ws = nullptr;
-            c->spec_ws_words = 0;
-            HIPCHK(dalloc(&c->spec_ws, need));
-            c->spec_ws_words = need;
-        }
-        const size_t fneed = exact_spec && !fast ? lcd::spec_fin_words(K, segs) : 0;
-        if (fneed > c->spec_fin_words) {
-            if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
-            dfree(c->spec_fin);
-            c->spec_fin = nullptr;
-            c->spec_fin_words = 0;
-            HIPCHK(dalloc(&c->spec_fin, fneed));
-            c->spec_fin_words = fneed;
-        }
-        if (K + 2 > c->spec_rr_cap) {
-            if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
-            dfree(c->spec_rr);
-            c->spec_rr = nullptr;
-            c->spec_rr_cap = 0;
-            HIPCHK(dalloc(&c->spec_rr, (size_t)K + 2));
-            HIPCHK(hipMemsetAsync(c->spec_rr, 0, 2 * sizeof(int32_t), c->stream));
-            c->spec_rr_cap = K + 2;
-        }
+    lc_stats ws{};
+    LCCHK(run_wgl(c, d, s.a, d->order, (int32_t)K, nullptr, K, s.analyzer, &ws));
+    LCCHK(readback(s));
+    float ms = 0, msw = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
+    if (K > 0) HIPCHK(hipEventElapsedTime(&msw, c->et3a, c->et3b));
+    if (st) {
+        *st = lc_stats{};
+        st->kernel_ms = ms;
+        st->wgl_ms = msw;
+        st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s.t0).count();
+        st->lds_keys = c->hctl[2];
+        st->wgl_keys = c->hctl[2];
+        st->wgl_steps = c->hctl[1];
+        st->events = c->hctl[1];
+        st->probes = c->hctl[0];  // Lowe's cache lookups
+        st->wgl_spilled = ws.wgl_spilled;
     }
-    // The speculative segments read 16-bit event words in place; every other
-    // kernel reads the 32-bit form, widened here once per upload.
-    const uint16_t *ev16 = (spec && d->events16) ? d->events16 : nullptr;
-    const uint32_t t0_path = K == 0 || d->table ? LC_T0_PATH_NONE
-                             : split            ? LC_T0_PATH_SEGMENTS
-                             : spec             ? LC_T0_PATH_SPEC
-                                                : LC_T0_PATH_LATTICE;
-    if (!ev16 && !d->ev32_ready && d->n_events) {
-        const uint64_t n4 = (d->n_events + 3) / 4;
-        const int blocks = (int)std::min<uint64_t>((n4 + 255) / 256, (uint64_t)c->cu_count * 8);
-        hipLaunchKernelGGL(k_widen16, dim3(std::max(blocks, 1)), dim3(256), 0, c->stream, d->events16, d->events,
-                           d->n_events);
-        HIPCHK(hipGetLastError());
-        d->ev32_ready = true;
-    }
-    uint32_t ticket_base = 0;
-    if (t0_step && c->ticket_live && !competition) {
-        ticket_base = c->ticket_next;
+    return LC_OK;
+}
+
+// Grow a device buffer the speculative segments work in to `need` elements
+// (an enqueued step may still be using the one it replaces).
+template <class T, class N>
+static int grow_dev(Dev *c, T *&ptr, N &have, N need) {
+    if (need <= have) return LC_OK;
+    if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
+    dfree(ptr);
+    have = 0;
+    HIPCHK(dalloc(&ptr, (size_t)need));
+    have = need;
+    return LC_OK;
+}
+
+// k_spec's per-key workspaces, the exact runs' saved sets, the rerun list.
+static int ensure_spec_ws(const Step &s) {
+    Dev *c = s.c;
+    LCCHK(grow_dev(c, c->spec_ws, c->spec_ws_words, lcd::spec_ws_words(s.K, s.p.segs)));
+    LCCHK(grow_dev(c, c->spec_fin, c->spec_fin_words, s.p.exact ? lcd::spec_fin_words(s.K, s.p.segs) : (size_t)0));
+    const int64_t rr_had = c->spec_rr_cap;
+    LCCHK(grow_dev(c, c->spec_rr, c->spec_rr_cap, s.K + 2));
+    if (c->spec_rr_cap != rr_had) HIPCHK(hipMemsetAsync(c->spec_rr, 0, 2 * sizeof(int32_t), c->stream));
+    return LC_OK;
+}
+
+// T0's Args -- every key, LPT order; keys outside the register lattice spill
+// to T1 -- and the ticket the step starts from: a T0-only step continues the
+// previous one's, any other zeroes the control block.
+static int t0_args(Step &s, lcd::Args *a0) {
+    Dev *c = s.c;
+    if (s.p.t0_step && c->ticket_live && !s.p.competition) {
+        s.ticket_base = c->ticket_next;
     } else {
-        // zero everything but the error words (a malformed batch reported at
-        // the next wait keeps them until then)
-        HIPCHK(hipMemsetAsync(c->ctl, 0, 4 * sizeof(unsigned long long) + 4 * sizeof(int32_t), c->stream));
-        HIPCHK(hipMemsetAsync(c->counters + 6, 0, 10 * sizeof(int32_t), c->stream));
+        LCCHK(zero_control(c));
     }
     c->ticket_live = false;
-    if (a.n_final && K > 0) HIPCHK(hipMemsetAsync(a.n_final, 0, (size_t)K * 4, c->stream));
-    // T0: every key, LPT order; keys outside the register lattice spill to T1
-    lcd::Args a0 = a;
-    a0.order = d->order; a0.n_order = (int32_t)K; a0.n_in = nullptr; a0.ticket = c->counters + 8;
-    a0.spill = spill0; a0.n_spill = n_spill0; a0.wide = wide; a0.n_wide = n_wide;
-    a0.deep = spill2; a0.n_deep = n_spill2;  // very wide keys: straight to T3
-    // T0 has two builds: 16 lattice registers (n <= 10 pending in VGPRs, 2
-    // waves per SIMD) when every key can be resident at once -- each key's
-    // events are serial, so there per-key latency is the whole story -- and
-    // 4 registers (9-10 pending in LDS, 4 waves per SIMD) for larger batches,
-    // where occupancy hides latency across keys.
-    const bool t0_wide = K <= (int64_t)c->cu_count * 8;
-    const int g0 = (int)std::max<int64_t>(1, std::min<int64_t>(K, (int64_t)c->cu_count * (t0_wide ? 8 : 16)));
-    a0.lat_ws = nullptr;
-    // T0 reads the result/counter/list pointers from a device copy of its
-    // Args: a ring slot holding these Args, else the next slot, refreshed
-    // (device copies are rewritten in stream order, after the launches that
-    // read them)
+    if (s.a.n_final && s.K > 0) HIPCHK(hipMemsetAsync(s.a.n_final, 0, (size_t)s.K * 4, c->stream));
+    const Lists l = lists_of(c);
+    *a0 = s.a;
+    a0->order = s.d->order; a0->n_order = (int32_t)s.K; a0->n_in = nullptr; a0->ticket = c->counters + 8;
+    a0->spill = l.spill0; a0->n_spill = l.n_spill0; a0->wide = l.wide; a0->n_wide = l.n_wide;
+    a0->deep = l.spill2; a0->n_deep = l.n_spill2;  // very wide keys: straight to T3
+    a0->lat_ws = nullptr;
+    return LC_OK;
+}
+
+// T0 reads the result/counter/list pointers from a device copy of its
+// Args: a ring slot holding these Args, else the next slot, refreshed
+// (device copies are rewritten in stream order, after the launches that
+// read them)
+static int args_slot(Dev *c, const lcd::Args &a0, lcd::Args **dargs) {
     int aslot = -1;
     for (int q = 0; q < Dev::ARGS_RING && aslot < 0; ++q)
         if (c->args_ok[q] && std::memcmp(c->hargs + q, &a0, sizeof a0) == 0) aslot = q;
@@ -1454,239 +1410,297 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
         HIPCHK(hipEventRecord(c->args_ev[aslot], c->stream));
         c->args_ok[aslot] = true;
     }
-    lcd::Args *const dargs = c->dargs + aslot;
-    // timing events only where their times are read (each recorded event
-    // costs the stream a few microseconds between kernels): an enqueued step
-    // is timed by the span ea0 .. ea1 alone
-    if (!async) HIPCHK(hipEventRecord(c->e0, c->stream));
-    if (async && c->n_async == 0) HIPCHK(hipEventRecord(c->ea0, c->stream));
-    const bool side_validate = K > 0 && ((a.strict && !spec) || gen_validate);
-    if (side_validate) {
-        // the event-by-event validation the host skipped: on the second
-        // stream, beside T0, joined before the set tiers and the readback
+    *dargs = c->dargs + aslot;
+    return LC_OK;
+}
+
+static lcd::SegArgs seg_args(const Step &s, int grid) {
+    Dev *c = s.c;
+    const DevBatch *d = s.d;
+    const lcd::Args &a = s.a;
+    lcd::SegArgs sa{};
+    sa.ev_off = d->ev_off; sa.events = d->events; sa.trans = d->trans; sa.key_error = d->key_error;
+    sa.n_trans = (uint32_t)d->n_trans; sa.n_keys = (int32_t)s.K; sa.max_seg = lcd::SEG_MAX;
+    // segments of about fill x (resident waves / keys) per key
+    const double per_key = std::max(1.0, 2.0 * grid / (double)s.K);
+    sa.seg_len = (uint32_t)std::max<double>(64.0, (double)d->n_events / (double)s.K / per_key);
+    if (c->o->seg_len > 0) sa.seg_len = (uint32_t)c->o->seg_len;
+    sa.seg_cnt = c->seg_cnt; sa.seg_end = c->seg_end; sa.seg_out = c->seg_out; sa.seg0_fev = c->seg0_fev;
+    sa.work = c->seg_work; sa.rerun = c->seg_rerun; sa.rerun_init = c->seg_rerun_init; sa.ctl = c->seg_ctl;
+    sa.err = a.err; sa.valid = a.valid; sa.fail_event = a.fail_event; sa.cause = a.cause;
+    sa.rec = a.rec;
+    sa.strict = a.strict;
+    sa.err_base = a.err_base;
+    return sa;
+}
+
+static lcd::SpecLaunch spec_launch(const Step &s) {
+    Dev *c = s.c;
+    const lc_opts &o = *c->o;
+    lcd::SpecLaunch l{};
+    l.segs = s.p.segs;
+    l.ws = c->spec_ws; l.rr = c->spec_rr; l.parity = c->spec_parity;
+    // (spec_ck == 0: the defaults; else (ck1 + 1) | (ck2 + 1) << 16)
+    l.ck1 = o.spec_ck ? ((uint32_t)o.spec_ck & 0xFFFFu) - 1u : 32u;
+    l.ck2 = o.spec_ck ? ((uint32_t)o.spec_ck >> 16) - 1u : 120u;
+    // the rerun launch usually finds no key, so one block per CU keeps its
+    // dispatch short; a longer rerun list walks the grid (16 and 64 blocks
+    // measured the same as 256 on C2 in round 5, 0.2552-0.2556 ms per step)
+    l.rerun_grid = c->cu_count;
+    l.validate_blocks = s.p.spec_vblocks;
+    l.events16 = s.p.ev16 ? s.d->events16 : nullptr;
+    l.cost_cuts = (o.path_flags & LC_PATH_SPEC_COST) != 0;
+    l.prio = !(o.path_flags & LC_PATH_SPEC_NOPRIO);
+    l.vfirst = s.p.spec_vfirst;
+    l.fin = s.p.exact ? c->spec_fin : nullptr;
+    l.stage = !(o.path_flags & LC_PATH_SPEC_NOSTAGE);
+    return l;
+}
+
+// The register tier's launch -- key segments, speculative segments or the
+// lattice; none for a table model -- with the validation the host skipped
+// beside it on the second stream where the plan says so, joined before the
+// set tiers and the readback.
+static int launch_register_tier(Step &s, const lcd::Args &a0, const lcd::Args *dargs) {
+    Dev *c = s.c;
+    const lc::StepPlan &p = s.p;
+    const int64_t K = s.K;
+    if (p.side_validate) {
         HIPCHK(hipEventRecord(c->vin, c->stream));
         HIPCHK(hipStreamWaitEvent(c->vstream, c->vin, 0));
-        lcd::Args av = a;
+        lcd::Args av = s.a;
         av.n_order = (int32_t)K;
-        HIPCHK(lcd::launch_validate(av, c->vstream, gen_validate));
+        HIPCHK(lcd::launch_validate(av, c->vstream, p.gen_validate));
         HIPCHK(hipEventRecord(c->vdone, c->vstream));
     }
-    if (split) {
-        lcd::SegArgs sa{};
-        sa.ev_off = d->ev_off; sa.events = d->events; sa.trans = d->trans; sa.key_error = d->key_error;
-        sa.n_trans = (uint32_t)d->n_trans; sa.n_keys = (int32_t)K; sa.max_seg = lcd::SEG_MAX;
-        // segments of about fill x (resident waves / keys) per key
+    // (et0 only where its time is read: each recorded event costs the stream
+    // a few microseconds between kernels)
+    if (p.split) {
         const int grid = c->cu_count * 12;
-        const double per_key = std::max(1.0, 2.0 * grid / (double)K);
-        sa.seg_len = (uint32_t)std::max<double>(64.0, (double)d->n_events / (double)K / per_key);
-        if (o.seg_len > 0) sa.seg_len = (uint32_t)o.seg_len;
-        sa.seg_cnt = c->seg_cnt; sa.seg_end = c->seg_end; sa.seg_out = c->seg_out; sa.seg0_fev = c->seg0_fev;
-        sa.work = c->seg_work; sa.rerun = c->seg_rerun; sa.rerun_init = c->seg_rerun_init; sa.ctl = c->seg_ctl;
-        sa.err = a.err; sa.valid = a.valid; sa.fail_event = a.fail_event; sa.cause = a.cause;
-        sa.rec = a.rec;
-        sa.strict = a.strict;
-        sa.err_base = a.err_base;
         HIPCHK(hipMemsetAsync(c->seg_ctl, 0, 4 * sizeof(int32_t), c->stream));
-        HIPCHK(lcd::launch_segments(sa, grid, c->stream));
-        if (!async) HIPCHK(hipEventRecord(c->et0, c->stream));
-    } else if (spec) {
-        // (spec_ck == 0: the defaults; else (ck1 + 1) | (ck2 + 1) << 16)
-        const uint32_t ck1 = o.spec_ck ? ((uint32_t)o.spec_ck & 0xFFFFu) - 1u : 32u;
-        const uint32_t ck2 = o.spec_ck ? ((uint32_t)o.spec_ck >> 16) - 1u : 120u;
-        // the validation of a host-unchecked batch runs in extra blocks of
-        // the same launch (a second stream cost ~40 us of cross-stream waits)
-        const int vblocks = a.strict ? (int)std::min<int64_t>(K, c->cu_count) : 0;
-        HIPCHK(lcd::launch_spec(a0, dargs, segs, c->spec_ws, c->spec_rr, c->spec_parity, ck1, ck2,
-                                // (rerun blocks: the launch usually finds no
-                                // key, so one block per CU keeps its dispatch
-                                // short; a longer rerun list walks the grid)
-                                LC_SPEC_RERUN_BLOCKS > 0 ? LC_SPEC_RERUN_BLOCKS : c->cu_count, vblocks, ev16,
-                                (o.path_flags & LC_PATH_SPEC_COST) != 0,
-                                !(o.path_flags & LC_PATH_SPEC_NOPRIO),
-                                K * segs > (int64_t)c->cu_count * 16,  // more keys than one resident round
-                                exact_spec && !fast ? c->spec_fin : nullptr,
-                                !(o.path_flags & LC_PATH_SPEC_NOSTAGE), c->stream));
+        HIPCHK(lcd::launch_segments(seg_args(s, grid), grid, c->stream));
+        if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
+    } else if (p.spec) {
+        HIPCHK(lcd::launch_spec(a0, dargs, spec_launch(s), c->stream));
         c->spec_parity ^= 1;
-        if (!async) HIPCHK(hipEventRecord(c->et0, c->stream));
-    } else if (K > 0 && !d->table) {
-        HIPCHK(lcd::launch_t0(a0, dargs, g0, t0_wide, c->stream, ticket_base));
-        if (!async) HIPCHK(hipEventRecord(c->et0, c->stream));
+        if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
+    } else if (K > 0 && !s.d->table) {
+        HIPCHK(lcd::launch_t0(a0, dargs, p.g0, p.t0_wide, c->stream, s.ticket_base));
+        if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
     } else if (K > 0) {
         HIPCHK(hipEventRecord(c->et0, c->stream));  // a table model: no register lattice
     }
-    if (side_validate) HIPCHK(hipStreamWaitEvent(c->stream, c->vdone, 0));
-    if (async) {
-        // (the span's end, ea1, is recorded by dev_wait after the last
-        // enqueued step: one timing event per step cost the stream a few
-        // microseconds between searches)
-        HIPCHK(hipEventRecord(c->ring[c->async_seq % 4], c->stream));
-        c->ea1_pending = true;
-        ++c->async_seq;
-        ++c->n_async;
-        c->ticket_next = (split || spec) ? ticket_base : ticket_base + (uint32_t)K + (uint32_t)g0;
-        c->ticket_live = true;
-        if (st) {  // times come from lc_wait
-            *st = lc_stats{};
-            st->t0_path = t0_path;
-            st->ev_word_bytes = t0_path ? (ev16 ? 2u : 4u) : 0u;
-        }
-        if (enqueued) *enqueued = true;
-        return LC_OK;
+    if (p.side_validate) HIPCHK(hipStreamWaitEvent(c->stream, c->vdone, 0));
+    return LC_OK;
+}
+
+// Where the next T0-only step's ticket continues from.
+static void keep_ticket(const Step &s) {
+    s.c->ticket_next = (s.p.split || s.p.spec) ? s.ticket_base : s.ticket_base + (uint32_t)s.K + (uint32_t)s.p.g0;
+    s.c->ticket_live = true;
+}
+
+// The end of an enqueued step: its ring event, nothing read back.
+static int finish_async(const Step &s, lc_stats *st, bool *enqueued) {
+    Dev *c = s.c;
+    // (the span's end, ea1, is recorded by dev_wait after the last
+    // enqueued step: one timing event per step cost the stream a few
+    // microseconds between searches)
+    HIPCHK(hipEventRecord(c->ring[c->async_seq % 4], c->stream));
+    c->ea1_pending = true;
+    ++c->async_seq;
+    ++c->n_async;
+    keep_ticket(s);
+    if (st) {  // times come from lc_wait
+        *st = lc_stats{};
+        st->t0_path = s.p.t0_path;
+        st->ev_word_bytes = s.p.ev_word_bytes;
     }
-    if (K > 0 && !t0_step) {
-        // T1: LDS hash sets
-        lcd::Args a1 = a;
-        a1.order = spill0; a1.n_order = 0; a1.n_in = n_spill0; a1.ticket = c->counters + 9;
-        if (d->table) { a1.order = d->order; a1.n_order = (int32_t)K; a1.n_in = nullptr; }  // every key
-        a1.spill = spill1; a1.n_spill = n_spill1; a1.wide = wide; a1.n_wide = n_wide;
-        int g1 = (int)std::min<int64_t>(K, (int64_t)c->cu_count * 7);
-        HIPCHK(lcd::launch_t1(a1, g1, c->stream));
-        // T2: keys that outgrew T1
-        lcd::Args a2 = a;
-        a2.order = spill1; a2.n_order = 0; a2.n_in = n_spill1; a2.ticket = c->counters + 10;
-        a2.spill = spill2; a2.n_spill = n_spill2; a2.wide = wide; a2.n_wide = n_wide;
-        HIPCHK(lcd::launch_t2(a2, c->cu_count, c->stream));
+    if (enqueued) *enqueued = true;
+    return LC_OK;
+}
+
+// T1 (LDS hash sets) over the keys T0 spilled -- every key of a table model
+// -- then T2 over the keys that outgrew T1.
+static int run_set_tiers(const Step &s) {
+    Dev *c = s.c;
+    const Lists l = lists_of(c);
+    lcd::Args a1 = s.a;
+    a1.order = l.spill0; a1.n_order = 0; a1.n_in = l.n_spill0; a1.ticket = c->counters + 9;
+    if (s.d->table) { a1.order = s.d->order; a1.n_order = (int32_t)s.K; a1.n_in = nullptr; }  // every key
+    a1.spill = l.spill1; a1.n_spill = l.n_spill1; a1.wide = l.wide; a1.n_wide = l.n_wide;
+    int g1 = (int)std::min<int64_t>(s.K, (int64_t)c->cu_count * 7);
+    HIPCHK(lcd::launch_t1(a1, g1, c->stream));
+    lcd::Args a2 = s.a;
+    a2.order = l.spill1; a2.n_order = 0; a2.n_in = l.n_spill1; a2.ticket = c->counters + 10;
+    a2.spill = l.spill2; a2.n_spill = l.n_spill2; a2.wide = l.wide; a2.n_wide = l.n_wide;
+    HIPCHK(lcd::launch_t2(a2, c->cu_count, c->stream));
+    return LC_OK;
+}
+
+// The end of a synchronous T0-only step: only the error words come back,
+// unless the results go to host memory.
+static int read_t0_step(const Step &s) {
+    Dev *c = s.c;
+    int rc;
+    if (s.mode != RES_HOST) {
+        HIPCHK(hipEventRecord(c->e1, c->stream));
+        HIPCHK(hipMemcpyAsync(c->hctl + 6, c->counters + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        rc = take_error(c);
+    } else {
+        rc = readback(s);
     }
+    std::memset(c->hctl, 0, CTL_BYTES);  // counters not kept on this path
+    keep_ticket(s);
+    return rc;
+}
+
+// T3 (HBM tier): keys beyond T2 (s.n_deep), then keys needing wide configs.
+// Each launch's workspace is sized from the counts the one before it left.
+static int run_hbm_tier(Step &s) {
+    Dev *c = s.c;
+    const Lists l = lists_of(c);
+    const int32_t *cnt = (const int32_t *)(c->hctl + 4);
+    s.t3 = true;
+    HIPCHK(hipEventRecord(c->et3a, c->stream));
+    lcd::Args a3 = s.a;
+    a3.wide = l.wide; a3.n_wide = l.n_wide;
+    // Narrow keys: the layered form first (<= 8 states; LC_PATH_LAYERS_OFF
+    // turns it off for A/B runs), the config-keyed narrow tier for the
+    // keys it hands on (cnt[6]).
+    // (the layered form steps ops as register-state masks: not a table model)
+    const bool layers = !s.d->table && !(c->o->path_flags & LC_PATH_LAYERS_OFF);
+    int32_t *narrow_list = l.spill2, *narrow_n = l.n_spill2;
+    int32_t n_narrow = s.n_deep;
+    int slots = 0;
+    if (s.n_deep > 0 && layers) {
+        LCCHK(ensure_lay_ws(c, s.n_deep, &slots));
+        a3.order = l.spill2; a3.n_order = 0; a3.n_in = l.n_spill2; a3.ticket = c->counters + 11;
+        a3.spill = l.old_narrow; a3.n_spill = c->counters + 6;
+        HIPCHK(lcd::launch_t3_layers(a3, c->lws.w, slots, c->stream));
+        HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        narrow_list = l.old_narrow; narrow_n = c->counters + 6;
+        n_narrow = cnt[6];
+    }
+    if (n_narrow > 0) {
+        LCCHK(ensure_ws(c, 0, n_narrow, &slots));
+        a3.order = narrow_list; a3.n_order = 0; a3.n_in = narrow_n; a3.ticket = c->counters + 13;
+        HIPCHK(lcd::launch_t3_narrow(a3, c->ws[0].w, slots, c->stream));
+        HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    if (cnt[3] > 0) {
+        LCCHK(ensure_ws(c, 1, cnt[3], &slots));
+        a3.order = l.wide; a3.n_order = 0; a3.n_in = l.n_wide; a3.ticket = c->counters + 12;
+        HIPCHK(lcd::launch_t3_wide(a3, c->ws[1].w, slots, c->stream));
+    }
+    HIPCHK(hipEventRecord(c->et3b, c->stream));
+    return readback(s);
+}
+
+// knossos.competition: the keys :linear left :unknown at its budget are
+// answered by WGL's search (the analysis that could still finish)
+static int run_competition(Step &s) {
+    Dev *c = s.c;
+    const unsigned long long *acc = c->hctl;
+    int32_t *const list = c->lists, *const count = c->counters + 20;  // (run_wgl zeroes [16..19])
+    HIPCHK(hipMemsetAsync(count, 0, sizeof(int32_t), c->stream));
+    HIPCHK(lcd::launch_collect_budget(s.a.cause, (int32_t)s.K, list, count, c->stream));
+    int32_t *h = (int32_t *)(c->hctl + 4) + 20;
+    HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(h, count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    const int32_t n_b = *h;
+    const uint64_t ev0 = acc[1];
+    if (n_b <= 0) return LC_OK;
+    lc_stats ws{};
+    LCCHK(run_wgl(c, s.d, s.a, list, 0, count, n_b, s.analyzer, &ws));
+    LCCHK(readback(s));
+    HIPCHK(hipEventElapsedTime(&s.msw, c->et3a, c->et3b));
+    HIPCHK(hipEventElapsedTime(&s.ms, c->e0, c->e1));
+    s.wgl_keys = (uint64_t)n_b;
+    s.wgl_steps = acc[1] - ev0;
+    s.wgl_spilled = ws.wgl_spilled;
+    return LC_OK;
+}
+
+static void fill_stats(const Step &s, lc_stats *st) {
+    const unsigned long long *acc = s.c->hctl;
+    st->kernel_ms = s.ms;
+    st->tier0_ms = s.ms0;
+    st->tier3_ms = s.ms3;
+    st->probes_t3 = s.t3 ? acc[0] - s.probes_pre_t3 : 0;
+    st->t3_bytes = s.t3 ? acc[3] : 0;
+    st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - s.t0).count();
+    st->probes = acc[0];
+    st->events = acc[1];
+    st->lds_keys = acc[2];
+    st->deep_keys = (uint64_t)(s.n_deep + s.n_widek);  // keys the HBM tier (re)searched
+    st->t0_path = s.p.t0_path;
+    st->ev_word_bytes = s.p.ev_word_bytes;
+    st->wgl_ms = s.msw;
+    st->wgl_keys = s.wgl_keys;
+    st->wgl_steps = s.wgl_steps;
+    st->wgl_spilled = s.wgl_spilled;
+}
+
+// Search d on c.  RES_HOST: r's arrays are host memory and receive the
+// results; RES_DEV: r's arrays are device memory on c; RES_CTX: results stay
+// in c's own device arrays (r unused).  allow_async: a step that is T0 alone
+// is only enqueued (*enqueued = true; errors surface at the next wait).
+// What runs is plan_step's choice (step_plan.hpp); this is the order it runs in.
+static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mode, bool allow_async, int64_t key0,
+                      lc_stats *st, bool *enqueued = nullptr, int64_t res_off = 0) {
+    lc::Range range("lincheck: search");
+    if (enqueued) *enqueued = false;
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(hipSetDevice(c->device));
+    const int64_t K = d->n_keys;
+    if (K > 0x7FFFFFFF) return lc::fail(LC_E_INVALID, "lc_check_device: too many keys");
+    LCCHK(ensure_capacity(c, K));
+    Step s{c, d, r, mode, K, t0};
+    step_args(s, key0, res_off);
+    s.p = lc::plan_step(step_in(s, allow_async));
+    const lc::StepPlan &p = s.p;
+    s.a.strict = p.strict ? 1 : 0;
+    if (s.analyzer && K > 0 && !p.wgl_only) HIPCHK(hipMemsetAsync(s.analyzer, LC_ALGO_LINEAR, (size_t)K, c->stream));
+    if (p.wgl_only) return search_wgl(s, st);
+    if (!p.async && c->ea1_pending) {  // the asynchronous steps' span ends before this one
+        HIPCHK(hipEventRecord(c->ea1, c->stream));
+        c->ea1_pending = false;
+    }
+    // an enqueued step reports a malformed batch through its own error words
+    if (p.async) s.a.err = c->counters + ERR_RING + 2 * (int)(c->async_seq % 4);
+    if (p.split) LCCHK(ensure_segments(c, K));
+    if (p.spec) LCCHK(ensure_spec_ws(s));
+    if (!p.ev16) LCCHK(ensure_ev32(c, d));
+    lcd::Args a0{}, *dargs = nullptr;  // (zeroed padding too: args_slot compares the bytes)
+    LCCHK(t0_args(s, &a0));
+    LCCHK(args_slot(c, a0, &dargs));
+    // timing events only where their times are read (each recorded event
+    // costs the stream a few microseconds between kernels): an enqueued step
+    // is timed by the span ea0 .. ea1 alone
+    if (!p.async) HIPCHK(hipEventRecord(c->e0, c->stream));
+    if (p.async && c->n_async == 0) HIPCHK(hipEventRecord(c->ea0, c->stream));
+    LCCHK(launch_register_tier(s, a0, dargs));
+    if (p.async) return finish_async(s, st, enqueued);
+    if (K > 0 && !p.t0_step) LCCHK(run_set_tiers(s));
     // One readback for the common case.  The T3 (HBM) tier is launched only
     // when T2 left keys for it (its workspace is sized from those counts),
     // after which the readback is repeated.
-    const unsigned long long *acc = c->hctl;
+    LCCHK(p.t0_step ? read_t0_step(s) : readback(s));
     const int32_t *cnt = (const int32_t *)(c->hctl + 4);
-    auto readback = [&]() -> int {
-        HIPCHK(hipEventRecord(c->e1, c->stream));
-        HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
-        if (mode == RES_HOST && K > 0) {
-            HIPCHK(hipMemcpyAsync(r->valid, c->valid, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(r->fail_event, c->fail_event, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipMemcpyAsync(r->cause, c->cause, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-            if (r->peak_configs)
-                HIPCHK(hipMemcpyAsync(r->peak_configs, c->peak, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            if (r->final_configs)
-                HIPCHK(hipMemcpyAsync(r->final_configs, c->final_cfg, (size_t)K * o.max_final * 16,
-                                      hipMemcpyDeviceToHost, c->stream));
-            if (r->n_final)
-                HIPCHK(hipMemcpyAsync(r->n_final, c->n_final, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-            if (r->analyzer)
-                HIPCHK(hipMemcpyAsync(r->analyzer, c->analyzer, (size_t)K, hipMemcpyDeviceToHost, c->stream));
-        }
-        HIPCHK(hipStreamSynchronize(c->stream));
-        return take_error(c);
-    };
-    if (t0_step) {
-        if (mode != RES_HOST) {
-            // only the error words come back
-            HIPCHK(hipEventRecord(c->e1, c->stream));
-            HIPCHK(hipMemcpyAsync(c->hctl + 6, c->counters + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            rc = take_error(c);
-        } else {
-            rc = readback();
-        }
-        std::memset(c->hctl, 0, CTL_BYTES);  // counters not kept on this path
-        c->ticket_next = (split || spec) ? ticket_base : ticket_base + (uint32_t)K + (uint32_t)g0;
-        c->ticket_live = true;
-        if (rc) return rc;
-    } else {
-        rc = readback();
-        if (rc) return rc;
-    }
-    bool t3 = false;
-    const unsigned long long probes_pre_t3 = acc[0];
-    const int32_t n_deep = cnt[2], n_widek = cnt[3];
-    if (K > 0 && (n_deep > 0 || n_widek > 0)) {
-        // T3 (HBM tier): keys beyond T2, then keys needing wide configs
-        t3 = true;
-        HIPCHK(hipEventRecord(c->et3a, c->stream));
-        lcd::Args a3 = a;
-        a3.wide = wide; a3.n_wide = n_wide;
-        // Narrow keys: the layered form first (<= 8 states; LC_PATH_LAYERS_OFF
-        // turns it off for A/B runs), the config-keyed narrow tier for the
-        // keys it hands on (cnt[6]).
-        // (the layered form steps ops as register-state masks: not a table model)
-        const bool layers = !d->table && !(o.path_flags & LC_PATH_LAYERS_OFF);
-        int32_t *narrow_list = spill2, *narrow_n = n_spill2;
-        int32_t n_narrow = n_deep;
-        if (n_deep > 0 && layers) {
-            int slots = 0;
-            rc = ensure_lay_ws(c, n_deep, &slots);
-            if (rc) return rc;
-            a3.order = spill2; a3.n_order = 0; a3.n_in = n_spill2; a3.ticket = c->counters + 11;
-            a3.spill = old_narrow; a3.n_spill = c->counters + 6;
-            HIPCHK(lcd::launch_t3_layers(a3, c->lws.w, slots, c->stream));
-            HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-            narrow_list = old_narrow; narrow_n = c->counters + 6;
-            n_narrow = cnt[6];
-        }
-        if (n_narrow > 0) {
-            int slots = 0;
-            rc = ensure_ws(c, 0, n_narrow, &slots);
-            if (rc) return rc;
-            a3.order = narrow_list; a3.n_order = 0; a3.n_in = narrow_n; a3.ticket = c->counters + 13;
-            HIPCHK(lcd::launch_t3_narrow(a3, c->ws[0].w, slots, c->stream));
-            HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));
-        }
-        if (cnt[3] > 0) {
-            int slots = 0;
-            rc = ensure_ws(c, 1, cnt[3], &slots);
-            if (rc) return rc;
-            a3.order = wide; a3.n_order = 0; a3.n_in = n_wide; a3.ticket = c->counters + 12;
-            HIPCHK(lcd::launch_t3_wide(a3, c->ws[1].w, slots, c->stream));
-        }
-        HIPCHK(hipEventRecord(c->et3b, c->stream));
-        rc = readback();
-        if (rc) return rc;
-    }
-    float ms = 0, ms0 = 0, ms3 = 0;
-    HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-    if (K > 0) HIPCHK(hipEventElapsedTime(&ms0, c->e0, c->et0));
-    if (t3) HIPCHK(hipEventElapsedTime(&ms3, c->et3a, c->et3b));
-    // knossos.competition: the keys :linear left :unknown at its budget are
-    // answered by WGL's search (the analysis that could still finish)
-    uint64_t wgl_keys = 0, wgl_steps = 0, wgl_spilled = 0;
-    float msw = 0;
-    if (competition && K > 0) {
-        int32_t *const list = c->lists, *const count = c->counters + 20;  // (run_wgl zeroes [16..19])
-        HIPCHK(hipMemsetAsync(count, 0, sizeof(int32_t), c->stream));
-        HIPCHK(lcd::launch_collect_budget(a.cause, (int32_t)K, list, count, c->stream));
-        int32_t *h = (int32_t *)(c->hctl + 4) + 20;
-        HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(h, count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        const int32_t n_b = *h;
-        const uint64_t ev0 = acc[1];
-        if (n_b > 0) {
-            lc_stats ws{};
-            rc = run_wgl(c, d, a, list, 0, count, n_b, analyzer, &ws);
-            if (rc) return rc;
-            rc = readback();
-            if (rc) return rc;
-            HIPCHK(hipEventElapsedTime(&msw, c->et3a, c->et3b));
-            HIPCHK(hipEventElapsedTime(&ms, c->e0, c->e1));
-            wgl_keys = (uint64_t)n_b;
-            wgl_steps = acc[1] - ev0;
-            wgl_spilled = ws.wgl_spilled;
-        }
-    }
-    if (st) {
-        st->kernel_ms = ms;
-        st->tier0_ms = ms0;
-        st->tier3_ms = ms3;
-        st->probes_t3 = t3 ? acc[0] - probes_pre_t3 : 0;
-        st->t3_bytes = t3 ? acc[3] : 0;
-        st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        st->probes = acc[0];
-        st->events = acc[1];
-        st->lds_keys = acc[2];
-        st->deep_keys = (uint64_t)(n_deep + n_widek);  // keys the HBM tier (re)searched
-        st->t0_path = t0_path;
-        st->ev_word_bytes = t0_path ? (ev16 ? 2u : 4u) : 0u;
-        st->wgl_ms = msw;
-        st->wgl_keys = wgl_keys;
-        st->wgl_steps = wgl_steps;
-        st->wgl_spilled = wgl_spilled;
-    }
+    s.probes_pre_t3 = c->hctl[0];
+    s.n_deep = cnt[2];
+    s.n_widek = cnt[3];
+    if (K > 0 && (s.n_deep > 0 || s.n_widek > 0)) LCCHK(run_hbm_tier(s));
+    HIPCHK(hipEventElapsedTime(&s.ms, c->e0, c->e1));
+    if (K > 0) HIPCHK(hipEventElapsedTime(&s.ms0, c->e0, c->et0));
+    if (s.t3) HIPCHK(hipEventElapsedTime(&s.ms3, c->et3a, c->et3b));
+    if (p.competition && K > 0) LCCHK(run_competition(s));
+    if (st) fill_stats(s, st);
     return LC_OK;
 }
 
@@ -1788,6 +1802,20 @@ static int prepare_batch(lc_ctx *c, const lc_batch *b, Shape *sh, const uint32_t
     return LC_OK;
 }
 
+// The part of r that holds the keys from k0 on: one device's share of a
+// result a context of several devices fills.
+static lc_result slice_result(const lc_result &r, int64_t k0, int max_final) {
+    lc_result s = r;
+    s.valid = r.valid + k0;
+    s.fail_event = r.fail_event + k0;
+    s.cause = r.cause + k0;
+    if (r.peak_configs) s.peak_configs = r.peak_configs + k0;
+    if (r.final_configs) s.final_configs = r.final_configs + (size_t)k0 * max_final * 2;
+    if (r.n_final) s.n_final = r.n_final + k0;
+    if (r.analyzer) s.analyzer = r.analyzer + k0;
+    return s;
+}
+
 // ---- C ABI ------------------------------------------------------------------
 
 extern "C" int lc_upload(lc_ctx *c, const lc_batch *b, lc_dev_batch **out) {
@@ -1836,17 +1864,9 @@ extern "C" int lc_check_device(lc_ctx *c, const lc_dev_batch *d, lc_result *r, i
         return dev_search(c->dev[0], d->part[0], r, dev_result ? RES_DEV : RES_HOST, (flags & LC_DEV_ASYNC) != 0, 0, st);
     auto t0 = std::chrono::steady_clock::now();
     std::vector<lc_stats> ps((size_t)c->n_dev);
-    const int mf = c->o.max_final;
     int rc = each_device(c, [&](int p) {
-        const int64_t k0 = d->key0[p];
-        lc_result rp = *r;
-        rp.valid = r->valid + k0;
-        rp.fail_event = r->fail_event + k0;
-        rp.cause = r->cause + k0;
-        if (r->peak_configs) rp.peak_configs = r->peak_configs + k0;
-        if (r->final_configs) rp.final_configs = r->final_configs + (size_t)k0 * mf * 2;
-        if (r->n_final) rp.n_final = r->n_final + k0;
-        return dev_search(c->dev[p], d->part[p], &rp, RES_HOST, false, k0, &ps[(size_t)p]);
+        const lc_result rp = slice_result(*r, d->key0[p], c->o.max_final);
+        return dev_search(c->dev[p], d->part[p], &rp, RES_HOST, false, d->key0[p], &ps[(size_t)p]);
     });
     if (rc) return rc;
     if (st) {
@@ -1921,7 +1941,6 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
     int64_t key0[MAX_DEV + 1];
     shard_keys(b, c->n_dev, key0);
     std::vector<lc_stats> ps((size_t)c->n_dev);
-    const int mf = c->o.max_final;
     rc = each_device(c, [&](int p) {
         Dev *d = c->dev[p];
         if (!d->staged) {
@@ -1933,16 +1952,8 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
         const uint32_t *es = src ? src + (b->n_keys ? b->ev_off[key0[p]] : 0) : nullptr;
         int e = upload_into(d, &s, d->staged, sh, sh.host_checked, es);
         if (e) return e;
-        const int64_t k0 = key0[p];
-        lc_result rp = *r;
-        rp.valid = r->valid + k0;
-        rp.fail_event = r->fail_event + k0;
-        rp.cause = r->cause + k0;
-        if (r->peak_configs) rp.peak_configs = r->peak_configs + k0;
-        if (r->final_configs) rp.final_configs = r->final_configs + (size_t)k0 * mf * 2;
-        if (r->n_final) rp.n_final = r->n_final + k0;
-        if (r->analyzer) rp.analyzer = r->analyzer + k0;
-        return dev_search(d, d->staged, &rp, RES_HOST, false, k0, &ps[(size_t)p]);
+        const lc_result rp = slice_result(*r, key0[p], c->o.max_final);
+        return dev_search(d, d->staged, &rp, RES_HOST, false, key0[p], &ps[(size_t)p]);
     });
     if (std::getenv("LC_TIMING")) {
         using ms = std::chrono::duration<double, std::milli>;
@@ -1960,9 +1971,6 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
 
 // ---- one process per GPU: node-wide verdict records ---------------------------
 
-// Pack this rank's verdicts (c's device arrays) into its block and all-gather
-// the blocks of every rank over RCCL (one rank: the block is the node), on
-// c's stream.
 // The rank's record block (and the node's), grown on demand; the search that
 // follows writes its records straight into the block (Dev::rec_out), and the
 // padding past the shard's n keys is zeroed.
@@ -1981,23 +1989,30 @@ static int node_buffers(lc_ctx *x, Dev *c, int64_t n, int64_t block) {
     return LC_OK;
 }
 
-static int gather_node(lc_ctx *x, Dev *c, int64_t n, int64_t block, bool packed = false) {
+// All-gather every rank's block (the records the search wrote) over RCCL on
+// c's stream; one rank: the block is the node.
+static int gather_node(lc_ctx *x, Dev *c, int64_t block) {
     lc::Range range("lincheck: gather");
-    const int64_t total = block * x->size;
     c->rec_out = nullptr;
-    if (block > 0 && !packed) {
-        const int threads = 256;
-        const int blocks = (int)std::min<int64_t>((block + threads - 1) / threads, 4096);
-        hipLaunchKernelGGL(k_pack_records, dim3(blocks), dim3(threads), 0, c->stream, c->valid, c->cause, c->fail_event,
-                           n, block, x->comm ? c->send : c->node);
-        HIPCHK(hipGetLastError());
-    }
     if (x->comm) {
         const Rccl *R = rccl();
         RCCLCHK(R->all_gather(c->send, c->node, (size_t)block, ncclUint64, x->comm, c->stream));
     }
-    c->node_n = total;
+    c->node_n = block * x->size;
     return LC_OK;
+}
+
+// Stops later searches writing records, on every return of a node step.
+struct RecOff {
+    Dev *d;
+    ~RecOff() { d->rec_out = nullptr; }
+};
+
+// A node step's error return: the copies out of the caller's arrays are waited for.
+static int drained(Dev *d, int e) {
+    (void)hipStreamSynchronize(d->cstream);
+    (void)hipStreamSynchronize(d->stream);
+    return e;
 }
 
 static int node_check_args(lc_ctx *c, int64_t n_keys, int64_t block) {
@@ -2025,10 +2040,7 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
     }
     rc = node_buffers(c, d, b->n_keys, block);
     if (rc) return rc;
-    struct RecOff {  // every return below stops later searches writing records
-        Dev *d;
-        ~RecOff() { d->rec_out = nullptr; }
-    } rec_off{d};
+    RecOff rec_off{d};
     const auto t_prep = std::chrono::steady_clock::now();
     // A large register-tier shard (throughput-bound: many keys per SIMD) is
     // uploaded and searched in NODE_CHUNKS key chunks: the copies run on a
@@ -2047,12 +2059,6 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
     const int chunks = can_chunk && big ? Dev::NODE_CHUNKS : 1;
     lc_result none{};
     bool enq = false;
-    // on an error below, the copies out of the caller's arrays are waited for
-    auto drained = [&](int e) {
-        (void)hipStreamSynchronize(d->cstream);
-        (void)hipStreamSynchronize(d->stream);
-        return e;
-    };
     std::chrono::steady_clock::time_point t_up;
     if (chunks > 1) {
         rc = ensure_capacity(d, K);
@@ -2062,14 +2068,14 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
         for (int i = 0; i < chunks; ++i) {
             if (!d->chunk[i]) {
                 d->chunk[i] = new (std::nothrow) DevBatch();
-                if (!d->chunk[i]) return drained(lc::fail(LC_E_NOMEM, "lc_check_node: out of memory"));
+                if (!d->chunk[i]) return drained(d, lc::fail(LC_E_NOMEM, "lc_check_node: out of memory"));
             }
             if (!d->chunk_ready[i]) HIPCHK(hipEventCreateWithFlags(&d->chunk_ready[i], hipEventDisableTiming));
             std::vector<uint64_t> off;
             const lc_batch s = sub_batch(b, key0[i], key0[i + 1], off);
             const uint32_t *es = src ? src + b->ev_off[key0[i]] : nullptr;
             rc = upload_into(d, &s, d->chunk[i], sh, sh.host_checked, es, false, d->cstream);
-            if (rc) return drained(rc);
+            if (rc) return drained(d, rc);
             HIPCHK(hipEventRecord(d->chunk_ready[i], d->cstream));
         }
         t_up = std::chrono::steady_clock::now();
@@ -2079,18 +2085,18 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
             rc = dev_search(d, d->chunk[i], &none, RES_CTX, true, key0[i], st, &e, key0[i]);
             enq = i == 0 ? e : (enq && e);
         }
-        if (rc) return drained(rc);
-        if (!enq) return drained(lc::fail(LC_E_DEVICE, "lc_check_node: a chunk left the register tier"));
+        if (rc) return drained(d, rc);
+        if (!enq) return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node: a chunk left the register tier"));
     } else {
         rc = upload_into(d, b, d->staged, sh, sh.host_checked, src, false);
         if (rc) return rc;
         t_up = std::chrono::steady_clock::now();
         rc = dev_search(d, d->staged, &none, RES_CTX, true, 0, st, &enq);
-        if (rc) return drained(rc);
+        if (rc) return drained(d, rc);
     }
     const auto t_search = std::chrono::steady_clock::now();
-    rc = gather_node(c, d, b->n_keys, block, true);  // the search wrote the records
-    if (rc) return drained(rc);
+    rc = gather_node(c, d, block);
+    if (rc) return drained(d, rc);
     // the records land in pinned memory (a copy into the caller's pageable
     // array would be a synchronous staged copy) and are copied out after the wait
     if (d->node_n > d->hnode_cap) {
@@ -2098,18 +2104,18 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
         d->hnode = nullptr;
         d->hnode_cap = 0;
         if (hipHostMalloc((void **)&d->hnode, (size_t)d->node_n * 8, hipHostMallocDefault) != hipSuccess)
-            return drained(lc::fail(LC_E_NOMEM, "lc_check_node: pinned record buffer"));
+            return drained(d, lc::fail(LC_E_NOMEM, "lc_check_node: pinned record buffer"));
         d->hnode_cap = d->node_n;
     }
     if (d->node_n && hipMemcpyAsync(d->hnode, d->node, (size_t)d->node_n * 8, hipMemcpyDeviceToHost, d->stream) !=
                          hipSuccess)
-        return drained(lc::fail(LC_E_DEVICE, "lc_check_node: record download failed"));
+        return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node: record download failed"));
     const auto t_gather = std::chrono::steady_clock::now();
     if (enq) {  // a T0-only step (or chunks): one wait for the search, the exchange and the download
         int n_async = 0;
         float span = 0;
         rc = dev_wait(d, &n_async, &span);
-        if (rc) return drained(rc);
+        if (rc) return drained(d, rc);
         if (st) st->kernel_ms = st->tier0_ms = span;
     } else {
         HIPCHK(hipStreamSynchronize(d->stream));
@@ -2189,17 +2195,9 @@ extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, 
                     rc = node_buffers(c, d, K, block);
                     if (rc) return rc;
                 }
-                struct RecOff {
-                    Dev *d;
-                    ~RecOff() { d->rec_out = nullptr; }
-                } rec_off{d};
-                auto drained = [&](int e) {
-                    (void)hipStreamSynchronize(d->cstream);
-                    (void)hipStreamSynchronize(d->stream);
-                    return e;
-                };
+                RecOff rec_off{d};
                 rc = upload_into(d, b, d->pipe[s], sh, sh.host_checked, src, false, d->cstream);
-                if (rc) return drained(rc);
+                if (rc) return drained(d, rc);
                 HIPCHK(hipEventRecord(d->pipe_ready[s], d->cstream));
                 // The host waits for the upload (the previous step's search
                 // is running meanwhile) and then enqueues the search: no
@@ -2210,15 +2208,15 @@ extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, 
                 lc_result none{};
                 bool enq = false;
                 rc = dev_search(d, d->pipe[s], &none, RES_CTX, true, 0, st, &enq);
-                if (rc) return drained(rc);
+                if (rc) return drained(d, rc);
                 if (direct) {
                     d->node_n = 0;  // the records are in `node` only (lc_node_records has none)
                 } else {
-                    rc = gather_node(c, d, K, block, true);
-                    if (rc) return drained(rc);
+                    rc = gather_node(c, d, block);
+                    if (rc) return drained(d, rc);
                     if (d->node_n && hipMemcpyAsync(node, d->node, (size_t)d->node_n * 8, hipMemcpyDeviceToHost,
                                                     d->stream) != hipSuccess)
-                        return drained(lc::fail(LC_E_DEVICE, "lc_check_node_async: record download failed"));
+                        return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node_async: record download failed"));
                 }
                 d->pipe_busy[s] = enq;
                 d->pipe_seq[s] = d->async_seq - 1;
@@ -2260,7 +2258,7 @@ extern "C" int lc_check_node_device(lc_ctx *c, const lc_dev_batch *db, int64_t b
     if (rc) return rc;
     rc = dev_search(d, db->part[0], &none, RES_CTX, (flags & LC_DEV_ASYNC) != 0, 0, st, &enq);
     if (rc) { d->rec_out = nullptr; return rc; }
-    rc = gather_node(c, d, db->n_keys, block, true);
+    rc = gather_node(c, d, block);
     if (rc) return rc;
     if (!enq) HIPCHK(hipStreamSynchronize(d->stream));
     return LC_OK;

@@ -2845,36 +2845,32 @@ __global__ __launch_bounds__(64 * SPEC_RERUN_WAVES) void k_spec_rerun(T0Args a) 
 
 size_t spec_ws_words(int64_t n_keys, int segs) { return (size_t)std::max<int64_t>(n_keys, 1) * segs * lat_ws_words(); }
 
-// Keys order[0 .. n_order) in workgroups of `segs` segments (2, 3, 4, 6 or
-// 8); rerun_grid: workgroups of the rerun launch at most; ws: spec_ws_words(n_order, segs) words; rr: n_order + 2 ints (two
-// rerun counts used in turn -- `parity` picks this launch's, which must be
-// zero, and k_spec_rerun zeroes the other -- then the rerun list).
-// validate: add the T0_STRICT validation blocks.
-// fin: exact segments (final configs wanted, no peaks): spec_fin_words(n_order,
-// segs) words for the runs' saved sets, segs 2, 4 or 8; null: closed sets.
 size_t spec_fin_words(int64_t n_keys, int segs) {
     return (size_t)std::max<int64_t>(n_keys, 1) * segs * 2 * SPEC_SAVE_WORDS;
 }
-hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, uint32_t *ws, int32_t *rr, int parity,
-                       uint32_t ck1, uint32_t ck2, int rerun_grid, int validate_blocks, const uint16_t *events16,
-                       bool cost_cuts, bool prio, bool vfirst, uint32_t *fin, bool stage, hipStream_t s) {
+// Keys order[0 .. n_order) in workgroups of l.segs segments, then the rerun
+// launch (device_search.hpp SpecLaunch).
+hipError_t launch_spec(const Args &a, const Args *a_dev, const SpecLaunch &l, hipStream_t s) {
+    const int segs = l.segs;
+    const uint16_t *const events16 = l.events16;
+    uint32_t *const fin = l.fin;
     T0Args t = make_t0(a, a_dev);
     t.events16 = events16;
-    if (cost_cuts) t.flags |= T0_SPEC_COST;
-    if (!stage) t.flags |= T0_SPEC_NOSTAGE;
-    if (vfirst && validate_blocks > 0) t.flags |= T0_SPEC_VFIRST;
-    if (!prio) t.flags |= T0_SPEC_NOPRIO;
-    t.lat_ws = ws;
-    t.spec_ck1 = ck1;
-    t.spec_ck2 = ck2;
-    t.spec_nrr = rr + (parity & 1);
-    t.spec_nrr_next = rr + ((parity & 1) ^ 1);
-    t.spec_rr = rr + 2;
+    if (l.cost_cuts) t.flags |= T0_SPEC_COST;
+    if (!l.stage) t.flags |= T0_SPEC_NOSTAGE;
+    if (l.vfirst && l.validate_blocks > 0) t.flags |= T0_SPEC_VFIRST;
+    if (!l.prio) t.flags |= T0_SPEC_NOPRIO;
+    t.lat_ws = l.ws;
+    t.spec_ck1 = l.ck1;
+    t.spec_ck2 = l.ck2;
+    t.spec_nrr = l.rr + (l.parity & 1);
+    t.spec_nrr_next = l.rr + ((l.parity & 1) ^ 1);
+    t.spec_rr = l.rr + 2;
     t.spec_fin = fin;
-    const dim3 grid((unsigned)std::max(1, a.n_order + std::max(0, validate_blocks)));
-    const dim3 rgrid((unsigned)std::max(1, std::min((a.n_order + SPEC_RERUN_WAVES - 1) / SPEC_RERUN_WAVES, rerun_grid)));
+    const dim3 grid((unsigned)std::max(1, a.n_order + std::max(0, l.validate_blocks)));
+    const dim3 rgrid((unsigned)std::max(1, std::min((a.n_order + SPEC_RERUN_WAVES - 1) / SPEC_RERUN_WAVES, l.rerun_grid)));
     // one wave per segment: more segments than waves (8, 12 or 16 on 4
-    // waves, 4 or 8 on 2) measured slower (device_api.hip)
+    // waves, 4 or 8 on 2) measured slower (step_plan.hpp)
 #define LC_SPEC_L(SS, E, X) hipLaunchKernelGGL((k_spec<SS, E, X>), grid, dim3(64 * SS), 0, s, t)
 #define LC_SPEC_ALL(E)                                      \
     if (fin) {                                              \

@@ -134,18 +134,27 @@ hipError_t launch_segments(const SegArgs &a, int grid, hipStream_t s);
 // a verdicts-only register-tier step, each a workgroup of `segs` waves (2, 3,
 // 4, 6, 8) searching segments from the full set and checking them against
 // each other, then a launch for the keys left to the unsegmented search;
-// results through a_dev like launch_t0.  rr: n_order + 2 ints of scratch
-// (both counts zero before the first launch; `parity` alternates).
-// validate_blocks > 0: the T0_STRICT validation runs in that many extra blocks.
+// results through a_dev like launch_t0.
 size_t spec_ws_words(int64_t n_keys, int segs);
-// events16: the batch's 16-bit event words (read in place), or null (the
-// 32-bit words); cost_cuts: cuts at equal estimated cost instead of equal
-// event counts;
-// prio: TOP walks' issue priority by progress (s_setprio).
 size_t spec_fin_words(int64_t n_keys, int segs);
-hipError_t launch_spec(const Args &a, const Args *a_dev, int segs, uint32_t *ws, int32_t *rr, int parity,
-                       uint32_t ck1, uint32_t ck2, int rerun_grid, int validate_blocks, const uint16_t *events16,
-                       bool cost_cuts, bool prio, bool vfirst, uint32_t *fin, bool stage, hipStream_t s);
+struct SpecLaunch {
+    int segs;                  // segments (one wave each) per key: 2, 3, 4, 6 or 8; with fin 2, 4 or 8
+    uint32_t *ws;              // spec_ws_words(n_order, segs) words: each wave's 9-10-pending workspace
+    int32_t *rr;               // n_order + 2 ints: two rerun counts used in turn, then the rerun list
+    int parity;                // picks this launch's count, which must be zero (both are before the
+                               // first launch; k_spec_rerun zeroes the other); alternates
+    uint32_t ck1, ck2;         // checkpoint distances of the verifying runs
+    int rerun_grid;            // workgroups of the rerun launch at most
+    int validate_blocks;       // > 0: the T0_STRICT validation runs in that many extra blocks
+    const uint16_t *events16;  // the batch's 16-bit event words (read in place), or null (the 32-bit words)
+    bool cost_cuts;            // cuts at equal estimated cost instead of equal event counts
+    bool prio;                 // TOP walks' issue priority by progress (s_setprio), else by wave age
+    bool vfirst;               // the validation blocks come first in the grid
+    uint32_t *fin;             // exact segments (final configs wanted, no peaks): spec_fin_words(n_order,
+                               // segs) words for the runs' saved sets; null: closed sets
+    bool stage;                // event words staged in LDS (false: read from HBM)
+};
+hipError_t launch_spec(const Args &a, const Args *a_dev, const SpecLaunch &l, hipStream_t s);
 uint32_t t0_max_width();   // most ops pending at once that T0 holds
 uint32_t t0_max_states();  // most register states T0 holds
 hipError_t launch_t1(const Args &a, int grid, hipStream_t s);

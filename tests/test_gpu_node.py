@@ -68,6 +68,21 @@ def test_logical_shards_more_than_keys():
     device_vs_oracle(h, dev)
 
 
+def test_logical_shards_wgl_analyzer():
+    """A resident :wgl check on two logical shards: each shard's analyzer
+    bytes land at its own keys (the second shard's used to overwrite the
+    first's, leaving the tail keys reading `linear`)."""
+    h = H.synth(n_keys=8, ops_per_key=40, concurrency=4, anomaly_rate=0.5, seed=74)
+    pk = Packed(h)
+    one = Device(0, algorithm=N.LC_ALGO_WGL).check(pk)
+    multi = Device(0, devices=[0, 0], algorithm=N.LC_ALGO_WGL).upload(pk).check()
+    assert multi.analyzer.tolist() == [N.LC_ALGO_WGL] * pk.n_keys
+    assert one.analyzer.tolist() == [N.LC_ALGO_WGL] * pk.n_keys
+    np.testing.assert_array_equal(multi.valid, one.valid)
+    np.testing.assert_array_equal(multi.fail_event, one.fail_event)
+    np.testing.assert_array_equal(multi.cause, one.cause)
+
+
 def _decode(rec, K):
     v, c, fe = P.unpack_records(rec.astype(np.int64))
     return v[:K], c[:K], fe[:K]
