@@ -521,7 +521,7 @@ __device__ __forceinline__ int ok_lane(uint32_t &W, uint32_t p, uint32_t live, u
 // to C(S), and W is already closed when no op was invoked since the last
 // :ok (`dirty` false): then the :ok is the projection alone.  Sets are
 // supersets of Knossos's, so this path is used only when no set size, probe
-// count or config list is asked for (FAST in lattice_key).
+// count or config list is asked for (FAST in lattice_walk).
 // Returns 0 normal, 1 invalid (W unchanged).
 template <int T, bool TAG = false>
 __device__ __forceinline__ int ok_lane_closed(uint32_t &W, uint32_t p, uint32_t live, uint32_t k_v, uint32_t cap_v,
@@ -935,51 +935,46 @@ extern "C" int lc_debug_t0_prof(unsigned long long *host) {
 }
 #endif
 
+// What a walk leaves behind for its caller's ending, beside the lattice W.
+struct LatWalk {
+    bool in_mem;      // the lattice lives in m.W (9 or 10 ops pending)
+    uint32_t slot_v;  // lane j: window slot of the op at index j
+    uint32_t live;    // occupied op indices
+    uint32_t n;       // ops pending
+    int status;       // 0, or 1 invalid, 2 budget, 3 spill: at event fev, W / live the set before it
+    uint32_t fev;
+    uint32_t peak, probes;
+};
+
+// The register tier's event walk: events evp[0 .. nev) from the start word
+// `init` in lane 0 (a state mask; TAG: one 6-bit group per start state,
+// xfer_tag), transitions trp[t], t < ntr.  The unsegmented search
+// (lattice_key) and the key segments (segment_search) both run it; the
+// speculative segments have a walk of their own (spec_walk).
 // FAST: no probe counting, no peak sizes and a budget no lattice can exceed
 // (>= 16 x 64 x 32 configs), so every size reduction and budget test folds
 // away -- the common case, and the bench's.
-template <int RM, bool FAST, bool E16 = false>
-__device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_t *ws) {
+template <int RM, bool FAST, bool TAG, class EvT>
+__device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, const EvT evp, const uint32_t nev,
+                                             const uint32_t *const trp, const uint32_t ntr, uint32_t init,
+                                             const LatMem &m, uint64_t budget, bool want_peak, bool count) {
+    static_assert(!TAG || (FAST && RM == T0_RSMALL), "tagged words: closed sets on the compact lattice only");
     const uint32_t lane = lane_id();
-    const LatMem m{ws, ws + T0_RMEM * 64, ws + 2 * T0_RMEM * 64};
-    const uint64_t eb = a.ev_off[key], ee = a.ev_off[key + 1];
-    const uint32_t tb = a.trans_off ? a.trans_off[key] : 0u;
-    if (a.key_error && a.key_error[key]) {  // lc_pack could not prepare it (check-safe)
-        finish_key(*a.full, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
-        return K_DONE;
-    }
-    if (a.key_states && a.key_states[key] > LC_WIDE_MAX_STATES) {
-        finish_key(*a.full, key, LC_UNKNOWN, LC_CAUSE_STATES, -1, 1, 0, 0);
-        return K_DONE;
-    }
-    const uint32_t nstates = a.trans_off ? (a.key_states ? a.key_states[key] : 0xFFFFu) : a.shared_states;
-    const uint32_t width = a.key_width ? a.key_width[key] : 0xFFu;  // = max ops pending at once
-    if (nstates > T0_MAX_STATES || width > T0_MAX_WIDTH || a.init_state >= T0_MAX_STATES) return K_SPILL;
-    const uint64_t budget = FAST ? ~0ull : a.budget;
-    const bool want_peak = !FAST && (a.flags & T0_WANT_PEAK) != 0;
-    const bool count = !FAST && (a.flags & T0_COUNT) != 0;
-    const EvSrc<E16> evp = ev_src<E16>(a) + eb;
-    // The key may name transitions trans[tb + t], t < ntr.  A batch the host
-    // did not validate may hold larger ids: they load nothing (the event is
-    // then a read of nil), and the batch's validation waves report them.
-    // Every other malformation (an :ok of a slot that is not pending, an
-    // :invoke into an occupied one) leaves T0 in bounds -- indices stay below
-    // T0_MAX_WIDTH and lanes below 64 -- with a verdict the failed call
-    // does not return.
-    const uint32_t ntr = a.n_trans > tb ? a.n_trans - tb : 0u;
-    const uint32_t *const trp = a.trans + (ntr ? tb : 0u);
-    const uint32_t nev = (a.flags & T0_DBG_NOEVENTS) ? 0u : (uint32_t)(ee - eb);
     auto ldesc = [&](uint32_t w, bool have) -> uint32_t {
         const uint32_t t = LC_EV_TRANS(w);
         return (have && !(w & LC_EV_OK_BIT) && t < ntr) ? trp[t] : 0u;
     };
+    auto decode = [](uint32_t d) -> Xfer {
+        if constexpr (TAG) return xfer_tag(d);
+        else return xfer_of(d);
+    };
 
-    uint32_t W[RM];
 #pragma unroll
     for (int k = 0; k < RM; ++k) W[k] = 0;
-    if (lane == 0) W[0] = 1u << a.init_state;
+    if (lane == 0) W[0] = init;
     bool in_mem = false;   // lattice lives in m.W (9 or 10 ops pending)
     uint32_t k_v = 0, cap_v = 0, b_v = 0;  // lane j: transfer (k, cap, b) of the op at index j
+    uint32_t m_v = 0;      // TAG: and its mask Mb
     uint32_t slot_v = 0;   // lane j: window slot of the op at index j
     uint32_t dense_v = 0;  // lane s: index of the op in window slot s
     uint32_t n = 0;        // ops pending
@@ -1000,7 +995,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
     uint32_t ev_nn = 128 + lane < nev ? evp[128 + lane] : 0u;
     // each lane decodes its event's transition once per chunk (VALU, all 64
     // at a time), so an invoke only reads three lanes
-    Xfer xc = xfer_of(dsc);
+    Xfer xc = decode(dsc);
     uint32_t e = 0, i = 0, base = 0;
     uint32_t lim = nev;  // 0 once the key has a verdict: each loop's only exit is its head
     auto advance = [&]() {
@@ -1008,7 +1003,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
         if (++i == 64u) {
             i = 0; base += 64;
             ev = ev_n; dsc = dsc_n; ev_n = ev_nn;
-            xc = xfer_of(dsc);
+            xc = decode(dsc);
             dsc_n = ldesc(ev_n, base + 64 + lane < nev);
             ev_nn = base + 128 + lane < nev ? evp[base + 128 + lane] : 0u;
         }
@@ -1053,6 +1048,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                     k_v = setl(k_v, idx, x.k);
                     cap_v = setl(cap_v, idx, x.cap);
                     b_v = setl(b_v, idx, x.b);
+                    if constexpr (TAG) m_v = setl(m_v, idx, (uint32_t)__builtin_amdgcn_readlane(xc.m, i));
                     dense_v = setl(dense_v, slot, idx);
                     live |= 1u << idx;
                     ++n;
@@ -1066,9 +1062,9 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                     // closed sets (compact build only: on C2's lone waves the
                     // projection's exposed bpermute ate the saved sweeps)
                     const uint32_t top = 32u - (uint32_t)__builtin_clz(live);
-                    if (top >= 6) r = ok_lane_closed<6>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty);
-                    else if (top == 5) r = ok_lane_closed<5>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty);
-                    else r = ok_lane_closed<4>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty);
+                    if (top >= 6) r = ok_lane_closed<6, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
+                    else if (top == 5) r = ok_lane_closed<5, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
+                    else r = ok_lane_closed<4, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
                     dirty = false;
                     k_v = setl(k_v, p, 0u);
                 } else {
@@ -1083,9 +1079,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                 // the specialised copies cost more in instruction-cache misses
                 // across a CU's four lone waves than they save.
                 const uint32_t top = 32u - (uint32_t)__builtin_clz(live);
-#ifndef LC_T0_WIDE_SPEC  // 1: specialise the wide build too (measured slower on C2)
-#define LC_T0_WIDE_SPEC 0
-                if ((RM == T0_RBIG && !LC_T0_WIDE_SPEC) || top >= 6)
+                if (RM == T0_RBIG || top >= 6)
                     r = ok_lane<6>(W0, p, live, k_v, cap_v, b_v, pk, pc, pb, lane, lm, budget, count, probes, nSn,
                                    want_peak);
                 else if (top == 5)
@@ -1095,7 +1089,6 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                     r = ok_lane<4>(W0, p, live, k_v, cap_v, b_v, pk, pc, pb, lane, lm, budget, count, probes, nSn,
                                    want_peak);
                 }
-#endif
                 live = r ? live : live & ~(1u << p);
                 n = r ? n : n - 1;
                 peak = nSn > peak ? nSn : peak;
@@ -1131,6 +1124,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                     k_v = setl(k_v, idx, x.k);
                     cap_v = setl(cap_v, idx, x.cap);
                     b_v = setl(b_v, idx, x.b);
+                    if constexpr (TAG) m_v = setl(m_v, idx, (uint32_t)__builtin_amdgcn_readlane(xc.m, i));
                     dense_v = setl(dense_v, slot, idx);
                     live |= 1u << idx;
                     ++n;
@@ -1139,13 +1133,17 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                 const uint32_t p = __builtin_amdgcn_readlane(dense_v, slot & 63u);
                 uint32_t nSn = 0;
                 int r;
-                if (n == 7) r = ok_reg<2>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
-                else if (n == 8) r = ok_reg<4>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
+                if (n == 7)
+                    r = ok_reg<2, RM, TAG>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak, m_v);
+                else if (n == 8)
+                    r = ok_reg<4, RM, TAG>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak, m_v);
                 else if constexpr (RM < 16) {
                     if (n == 9)
-                        r = ok_event_mem<8>(m, p, n, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
+                        r = ok_event_mem<8, TAG>(m, p, n, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak,
+                                                 m_v);
                     else
-                        r = ok_event_mem<16>(m, p, n, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
+                        r = ok_event_mem<16, TAG>(m, p, n, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak,
+                                                  m_v);
                 } else {
                     if (n == 9) r = ok_reg<8>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
                     else r = ok_reg<16>(W, p, k_v, cap_v, b_v, lane, budget, count, probes, nSn, want_peak);
@@ -1160,6 +1158,7 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
                     k_v = setl(k_v, p, x0);
                     cap_v = setl(cap_v, p, x1);
                     b_v = setl(b_v, p, x2);
+                    if constexpr (TAG) m_v = setl(m_v, p, (uint32_t)__builtin_amdgcn_readlane(m_v, last));
                     dense_v = setl(dense_v, s_last & 63u, p);
                     // index `last` is free now: zero transfer (the lane phase relies on it)
                     k_v = setl(k_v, last, 0u);
@@ -1186,23 +1185,75 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
 #undef T0_PROF_BEGIN
 #undef T0_PROF_END
     W[0] = W0;
-    if (status == 3) return K_SPILL;
+    out.in_mem = in_mem; out.slot_v = slot_v; out.live = live; out.n = n;
+    out.status = status; out.fev = fev; out.peak = peak; out.probes = probes;
+}
+
+// One key, unsegmented: K_DONE with its results written, or K_SPILL.
+template <int RM, bool FAST, bool E16 = false>
+__device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_t *ws) {
+    const uint32_t lane = lane_id();
+    const LatMem m{ws, ws + T0_RMEM * 64, ws + 2 * T0_RMEM * 64};
+    const uint64_t eb = a.ev_off[key], ee = a.ev_off[key + 1];
+    const uint32_t tb = a.trans_off ? a.trans_off[key] : 0u;
+    if (a.key_error && a.key_error[key]) {  // lc_pack could not prepare it (check-safe)
+        finish_key(*a.full, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
+        return K_DONE;
+    }
+    if (a.key_states && a.key_states[key] > LC_WIDE_MAX_STATES) {
+        finish_key(*a.full, key, LC_UNKNOWN, LC_CAUSE_STATES, -1, 1, 0, 0);
+        return K_DONE;
+    }
+    const uint32_t nstates = a.trans_off ? (a.key_states ? a.key_states[key] : 0xFFFFu) : a.shared_states;
+    const uint32_t width = a.key_width ? a.key_width[key] : 0xFFu;  // = max ops pending at once
+    if (nstates > T0_MAX_STATES || width > T0_MAX_WIDTH || a.init_state >= T0_MAX_STATES) return K_SPILL;
+    const uint64_t budget = FAST ? ~0ull : a.budget;
+    const bool want_peak = !FAST && (a.flags & T0_WANT_PEAK) != 0;
+    const bool count = !FAST && (a.flags & T0_COUNT) != 0;
+    // The key may name transitions trans[tb + t], t < ntr.  A batch the host
+    // did not validate may hold larger ids: they load nothing (the event is
+    // then a read of nil), and the batch's validation waves report them.
+    // Every other malformation (an :ok of a slot that is not pending, an
+    // :invoke into an occupied one) leaves T0 in bounds -- indices stay below
+    // T0_MAX_WIDTH and lanes below 64 -- with a verdict the failed call
+    // does not return.
+    const uint32_t ntr = a.n_trans > tb ? a.n_trans - tb : 0u;
+    const uint32_t nev = (a.flags & T0_DBG_NOEVENTS) ? 0u : (uint32_t)(ee - eb);
+    uint32_t W[RM];
+    LatWalk w;
+    lattice_walk<RM, FAST, false>(W, w, ev_src<E16>(a) + eb, nev, a.trans + (ntr ? tb : 0u), ntr, 1u << a.init_state, m,
+                                  budget, want_peak, count);
+    if (w.status == 3) return K_SPILL;
     // per-key epilogue (results through `full`); on a failure W / live still
     // hold the set before the failing event, which is what is reported
     const Args &f = *a.full;
 
-    if (!in_mem) {
+    if (!w.in_mem) {
 #pragma unroll
         for (int k = 0; k < RM; ++k) m.W[k * 64 + lane] = W[k];
     }
-    if (!(a.flags & T0_DBG_NOFINAL)) write_final_mem(f, key, m, lane, slot_v, live);
-    const uint32_t pr = __ockl_wfred_add_u32(probes);
-    if (status)
-        finish_key(f, key, status == 1 ? LC_INVALID : LC_UNKNOWN, status == 1 ? LC_CAUSE_NONLIN : LC_CAUSE_BUDGET,
-                   (int32_t)fev, peak, pr, (uint64_t)fev + (status == 1 ? 1u : 0u));
+    if (!(a.flags & T0_DBG_NOFINAL)) write_final_mem(f, key, m, lane, w.slot_v, w.live);
+    const uint32_t pr = __ockl_wfred_add_u32(w.probes);
+    if (w.status)
+        finish_key(f, key, w.status == 1 ? LC_INVALID : LC_UNKNOWN,
+                   w.status == 1 ? LC_CAUSE_NONLIN : LC_CAUSE_BUDGET, (int32_t)w.fev, w.peak, pr,
+                   (uint64_t)w.fev + (w.status == 1 ? 1u : 0u));
     else
-        finish_key(f, key, LC_VALID, LC_CAUSE_NONE, -1, peak, pr, nev);
+        finish_key(f, key, LC_VALID, LC_CAUSE_NONE, -1, w.peak, pr, nev);
     return K_DONE;
+}
+
+// A key the register tier cannot hold: to the deep or the spill list -- or,
+// in a step declared to fit T0 (T0_STRICT), malformed: no later tier runs.
+__device__ __forceinline__ void t0_spill(const T0Args &a, int32_t key) {
+    const Args &f = *a.full;
+    if (a.flags & T0_STRICT) {
+        t0_malformed(a, key, LC_BATCH_E_FIT);
+        finish_key(f, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
+    } else {
+        const bool deep = f.deep && a.key_width && a.key_width[key] > LC_DIRECT_T3_WIDTH;
+        push_list(deep ? f.deep : f.spill, deep ? f.n_deep : f.n_spill, key, f.list_cap);
+    }
 }
 
 // T0 over a work list: one wavefront per key (lattice in 4 registers, or the
@@ -1331,16 +1382,7 @@ __global__ __launch_bounds__(64) void k_search_lattice(T0Args a) {
         if ((uint32_t)w >= (uint32_t)a.n_order) break;
         const int32_t key = a.order[w];
         const int kr = fast ? lattice_key<RM, true>(a, key, ws) : lattice_key<RM, false>(a, key, ws);
-        if (kr == K_SPILL) {
-            const Args &f = *a.full;
-            if (a.flags & T0_STRICT) {  // declared to fit T0, and it does not: no later tier runs
-                t0_malformed(a, key, LC_BATCH_E_FIT);
-                finish_key(f, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
-            } else {
-                const bool deep = f.deep && a.key_width && a.key_width[key] > LC_DIRECT_T3_WIDTH;
-                push_list(deep ? f.deep : f.spill, deep ? f.n_deep : f.n_spill, key, f.list_cap);
-            }
-        }
+        if (kr == K_SPILL) t0_spill(a, key);
 #ifdef LC_T0_STAMPS
         ++nkeys;
         lastkey = (uint32_t)key;
@@ -1510,153 +1552,12 @@ __device__ __forceinline__ void segment_search(const SegArgs &a, int32_t key, ui
     constexpr int RM = T0_RSMALL;
     const uint32_t lane = lane_id();
     const LatMem m{ws, ws + T0_RMEM * 64, ws + 2 * T0_RMEM * 64};
-    const uint32_t *const evp = a.events + a.ev_off[key] + sb;
-    const uint32_t nev = se - sb;
-    const uint32_t ntr = a.n_trans;
-    auto ldesc = [&](uint32_t w, bool have) -> uint32_t {
-        const uint32_t t = LC_EV_TRANS(w);
-        return (have && !(w & LC_EV_OK_BIT) && t < ntr) ? a.trans[t] : 0u;
-    };
-    auto decode = [](uint32_t d) -> Xfer { return TAG ? xfer_tag(d) : xfer_of(d); };
     uint32_t W[RM];
-#pragma unroll
-    for (int k = 0; k < RM; ++k) W[k] = 0;
-    if (lane == 0) W[0] = init;
-    bool in_mem = false;
-    uint32_t k_v = 0, cap_v = 0, b_v = 0, m_v = 0;
-    uint32_t slot_v = 0, dense_v = 0, n = 0, live = 0;
-    uint32_t lm[6];
-#pragma unroll
-    for (int q = 0; q < 6; ++q) lm[q] = (uint32_t)__builtin_amdgcn_sbfe((int)lane, q, 1);
-    int status = 0;
-    uint32_t fev = 0;
-    uint32_t ev = lane < nev ? evp[lane] : 0u;
-    uint32_t dsc = ldesc(ev, lane < nev);
-    uint32_t ev_n = 64 + lane < nev ? evp[64 + lane] : 0u;
-    uint32_t dsc_n = ldesc(ev_n, 64 + lane < nev);
-    uint32_t ev_nn = 128 + lane < nev ? evp[128 + lane] : 0u;
-    Xfer xc = decode(dsc);
-    uint32_t e = 0, i = 0, base = 0, lim = nev;
-    auto advance = [&]() {
-        ++e;
-        if (++i == 64u) {
-            i = 0; base += 64;
-            ev = ev_n; dsc = dsc_n; ev_n = ev_nn;
-            xc = decode(dsc);
-            dsc_n = ldesc(ev_n, base + 64 + lane < nev);
-            ev_nn = base + 128 + lane < nev ? evp[base + 128 + lane] : 0u;
-        }
-    };
-    uint32_t W0 = W[0];
-    bool dirty = true;
-    for (uint32_t phase = 0; phase <= nev && e < lim; ++phase) {
-        while (e < lim) {  // lane phase: <= 6 pending
-            const uint32_t evi = __builtin_amdgcn_readlane(ev, i);
-            const uint32_t slot = LC_EV_SLOT(evi);
-            if (!(evi & LC_EV_OK_BIT)) {
-                if (n == 6) break;
-                if (n >= T0_MAX_WIDTH || slot >= 64) {
-                    status = 3;
-                } else {
-                    const uint32_t idx = (uint32_t)__builtin_ctz(~live);
-                    const bool me = lane == idx;
-                    slot_v = me ? slot : slot_v;
-                    k_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.k, i) : k_v;
-                    cap_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.cap, i) : cap_v;
-                    b_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.b, i) : b_v;
-                    if constexpr (TAG) m_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.m, i) : m_v;
-                    dense_v = lane == slot ? idx : dense_v;
-                    live |= 1u << idx;
-                    ++n;
-                    dirty = true;
-                }
-            } else {
-                const uint32_t p = __builtin_amdgcn_readlane(dense_v, slot & 63u);
-                const uint32_t top = 32u - (uint32_t)__builtin_clz(live);
-                int r;
-                if (top >= 6) r = ok_lane_closed<6, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
-                else if (top == 5) r = ok_lane_closed<5, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
-                else r = ok_lane_closed<4, TAG>(W0, p, live, k_v, cap_v, b_v, lane, lm, dirty, m_v);
-                dirty = false;
-                k_v = setl(k_v, p, 0u);
-                live = r ? live : live & ~(1u << p);
-                n = r ? n : n - 1;
-                status = r;
-                fev = e;
-            }
-            lim = status ? 0u : lim;
-            advance();
-        }
-        if (e >= lim) break;
-        W[0] = W0;
-#pragma unroll
-        for (int k = 1; k < RM; ++k) W[k] = 0u;
-        while (e < lim) {  // dense phase: 7-10 pending
-            const uint32_t evi = __builtin_amdgcn_readlane(ev, i);
-            const uint32_t slot = LC_EV_SLOT(evi);
-            if (!(evi & LC_EV_OK_BIT)) {
-                if (n >= T0_MAX_WIDTH || slot >= 64) {
-                    status = 3;
-                } else {
-                    if (n == 8) {  // 9 pending: the lattice moves to the workspace
-#pragma unroll
-                        for (int k = 0; k < T0_RMEM; ++k) m.W[k * 64 + lane] = k < RM ? W[k < RM ? k : 0] : 0u;
-                        in_mem = true;
-                    }
-                    const uint32_t idx = n;
-                    const bool me = lane == idx;
-                    slot_v = me ? slot : slot_v;
-                    k_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.k, i) : k_v;
-                    cap_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.cap, i) : cap_v;
-                    b_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.b, i) : b_v;
-                    if constexpr (TAG) m_v = me ? (uint32_t)__builtin_amdgcn_readlane(xc.m, i) : m_v;
-                    dense_v = lane == slot ? idx : dense_v;
-                    live |= 1u << idx;
-                    ++n;
-                }
-            } else {
-                const uint32_t p = __builtin_amdgcn_readlane(dense_v, slot & 63u);
-                uint32_t nSn = 0, probes = 0;
-                int r;
-                if (n == 7) r = ok_reg<2, RM, TAG>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false, m_v);
-                else if (n == 8) r = ok_reg<4, RM, TAG>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false, m_v);
-                else if (n == 9)
-                    r = ok_event_mem<8, TAG>(m, p, n, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false, m_v);
-                else
-                    r = ok_event_mem<16, TAG>(m, p, n, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false, m_v);
-                const uint32_t last = n - 1;
-                const uint32_t s_last = __builtin_amdgcn_readlane(slot_v, last);
-                const uint32_t x0 = __builtin_amdgcn_readlane(k_v, last), x1 = __builtin_amdgcn_readlane(cap_v, last),
-                               x2 = __builtin_amdgcn_readlane(b_v, last);
-                const uint32_t x3 = TAG ? __builtin_amdgcn_readlane(m_v, last) : 0u;
-                const bool mp = lane == p && !r;
-                slot_v = mp ? s_last : slot_v;
-                k_v = mp ? x0 : k_v;
-                cap_v = mp ? x1 : cap_v;
-                b_v = mp ? x2 : b_v;
-                if constexpr (TAG) m_v = mp ? x3 : m_v;
-                dense_v = (lane == s_last && !r) ? p : dense_v;
-                k_v = (lane == last && !r) ? 0u : k_v;
-                live = r ? live : (1u << last) - 1u;
-                if (in_mem && n == 9 && !r) {
-#pragma unroll
-                    for (int k = 0; k < RM; ++k) W[k] = m.W[k * 64 + lane];
-                    in_mem = false;
-                }
-                n = r ? n : n - 1;
-                status = r;
-                fev = e;
-            }
-            lim = status ? 0u : lim;
-            advance();
-            if (n <= 6) break;
-        }
-        W0 = W[0];
-        dirty = true;
-    }
-    W[0] = W0;
+    LatWalk w;
+    lattice_walk<RM, true, TAG>(W, w, ev_src<false>(a) + (a.ev_off[key] + sb), se - sb, a.trans, a.n_trans, init, m,
+                                ~0ull, false, false);
     uint32_t f = 0;
-    if (in_mem) {
+    if (w.in_mem) {
 #pragma unroll 1
         for (int k = 0; k < T0_RMEM; ++k) f |= m.W[k * 64 + lane];
     } else {
@@ -1665,9 +1566,9 @@ __device__ __forceinline__ void segment_search(const SegArgs &a, int32_t key, ui
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) f |= (uint32_t)__shfl_xor((int)f, o);
-    status_out = status;
-    fev_out = sb + fev;
-    fin_out = status ? 0u : f;
+    status_out = w.status;
+    fev_out = sb + w.fev;
+    fin_out = w.status ? 0u : f;
 }
 
 // Every segment of the work list, one wave each (persistent grid, tickets).
@@ -1691,11 +1592,8 @@ __global__ __launch_bounds__(64) void k_search_segments(SegArgs a) {
         if (lane_id() == 0) {
             a.seg_out[(size_t)key * a.max_seg + s] = fin;
             if (s == 0) a.seg0_fev[key] = status == 1 ? (int32_t)fev : -1;
-            if (status == 3) {  // declared to fit the register tier, and it does not
-                atomicOr(&a.err[0], LC_BATCH_E_FIT);
-                atomicMax(&a.err[1], a.err_base + key + 1);
-            }
         }
+        if (status == 3) t0_malformed(a, key, LC_BATCH_E_FIT);  // declared to fit the register tier, and it does not
     }
 }
 
@@ -1758,14 +1656,11 @@ __global__ __launch_bounds__(64) void k_seg_rerun(SegArgs a) {
         int status;
         uint32_t fev, fin;
         segment_search<false>(a, key, ends[s - 1], ends[s], a.rerun_init[w], ws, status, fev, fin);
-        if (lane_id() == 0) {
-            if (status == 1) {
-                seg_verdict(a, key, LC_INVALID, LC_CAUSE_NONLIN, (int32_t)fev);
-            } else {  // cannot happen for a consistent batch: report it as malformed
-                seg_verdict(a, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1);
-                atomicOr(&a.err[0], LC_BATCH_E_FIT);
-                atomicMax(&a.err[1], a.err_base + key + 1);
-            }
+        if (status == 1) {
+            if (lane_id() == 0) seg_verdict(a, key, LC_INVALID, LC_CAUSE_NONLIN, (int32_t)fev);
+        } else {  // cannot happen for a consistent batch: report it as malformed
+            if (lane_id() == 0) seg_verdict(a, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1);
+            t0_malformed(a, key, LC_BATCH_E_FIT);
         }
     }
 }
@@ -2830,16 +2725,7 @@ __global__ __launch_bounds__(64 * SPEC_RERUN_WAVES) void k_spec_rerun(T0Args a) 
          w += gridDim.x * SPEC_RERUN_WAVES) {
         const int32_t key = a.spec_rr[w];
         const int kr = lattice_key<T0_RSMALL, !EX, E16>(a, key, ws);
-        if (kr == K_SPILL) {
-            const Args &f = *a.full;
-            if (a.flags & T0_STRICT) {
-                t0_malformed(a, key, LC_BATCH_E_FIT);
-                finish_key(f, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
-            } else {
-                const bool deep = f.deep && a.key_width && a.key_width[key] > LC_DIRECT_T3_WIDTH;
-                push_list(deep ? f.deep : f.spill, deep ? f.n_deep : f.n_spill, key, f.list_cap);
-            }
-        }
+        if (kr == K_SPILL) t0_spill(a, key);
     }
 }
 
