@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LC_ABI_VERSION 11
+#define LC_ABI_VERSION 12
 
 /* ---- error codes --------------------------------------------------------- */
 #define LC_OK            0
@@ -392,7 +392,13 @@ typedef struct lc_opts {
                                       by every run, not staged in LDS once per key  */
 #define LC_PATH_WGL_EV_HBM   0x2000 /* WGL: every key's events read from HBM, none
                                        staged in LDS (tests of that walk; ABI 11)   */
-#define LC_PATH_ALL          0x3FFF
+#define LC_PATH_SET_HBM      0x4000 /* lc_set_check: every key with elements through the
+                                       HBM tier, none through the LDS tier (tests of
+                                       those kernels; ABI 12)                        */
+#define LC_PATH_SET_DIRECT   0x8000 /* lc_set_check, HBM tier: k_set_mark's bits leave by
+                                       atomics from the lanes, never through a
+                                       workgroup's LDS tile (A/B runs and tests)      */
+#define LC_PATH_ALL          0xFFFF
 
 /* lc_opts.flags */
 #define LC_OPT_COUNT_PROBES 0x1  /* count successor-config probes (lc_stats.probes,
@@ -615,6 +621,143 @@ int  lc_edn_write_named(const char *path, const lc_history *h, const char *const
 int  lc_fressian_read(const char *path, lc_hist **out);
 int  lc_fressian_parse(const uint8_t *buf, int64_t len, lc_hist **out);
 int  lc_fressian_write(const char *path, const lc_history *h);
+
+/* ---- the set workload (set.clj:42-49, ABI 12) -------------------------------- */
+/* The demo's second workload (etcdemo.clj:128-131, --workload set) is checked
+ * with (checker/set) at set.clj:46: every :add that was acknowledged must be
+ * in the final :read, and the read may hold only elements that were attempted.
+ * Restated from the public Jepsen 0.2.x source of jepsen.checker/set and
+ * jepsen.util/integer-interval-set-str (parity unpinned).
+ * This path has its own structs and entry points; nothing above changes. */
+/* :f of a set-workload op map */
+#define LC_SF_ADD   0
+#define LC_SF_READ  1
+#define LC_SF_OTHER 2   /* nemesis rows and anything else: contributes nothing */
+
+/*
+ * A raw set-workload history as struct-of-arrays, one row per op map, in
+ * history order.
+ *   key        the k of an independent tuple [k v], or LC_NO_KEY; NULL = no row
+ *              has one (the demo's single "a-set")
+ *   elem       an :add row's element (LC_NIL: nil or not an integer); a :read
+ *              row: LC_NIL when its :value is nil, else 0
+ *   read_off   row r's read collection is read_elem[read_off[r] .. read_off[r+1])
+ *              (empty for rows that are no :read; an element that is nil or
+ *              not an integer is LC_NIL); both may be NULL when no row reads
+ *   index      the op's :index; may be NULL
+ */
+typedef struct lc_set_history {
+    int64_t        n;
+    const uint8_t *type;      /* LC_INVOKE / LC_OK_T / LC_FAIL / LC_INFO */
+    const uint8_t *f;         /* LC_SF_*                                  */
+    const int64_t *key;
+    const int64_t *elem;
+    const int64_t *read_off;  /* [n + 1] */
+    const int64_t *read_elem;
+    const int64_t *index;
+} lc_set_history;
+
+/* class byte of an add id */
+#define LC_SET_ATTEMPT 1  /* an :invoke :add */
+#define LC_SET_ACK     2  /* an :ok :add     */
+/* per-key status */
+#define LC_SET_KEY_OK         0
+#define LC_SET_KEY_NEVER_READ 1  /* no :ok :read, or the last one's value is nil:
+                                    {:valid? :unknown :error "Set was never read"} */
+#define LC_SET_KEY_ERROR      2  /* a nil or non-integer element (check-safe
+                                    around that key): :unknown with an error     */
+
+/*
+ * A packed set batch: lc_set_pack's output or caller-built.  Key k's elements
+ * are numbered by ids below span[k]:
+ *   rank[k] == 0  offset ids: element = min[k] + id
+ *   rank[k] == 1  rank ids:   element = vals[vals_off[k] + id], vals ascending
+ *                 and distinct, vals_off[k + 1] - vals_off[k] >= span[k]
+ * base[k] is the key's offset, in 64-bit words, into each of the three
+ * bitmaps (attempted, acknowledged, read) of n_words words: even, ascending,
+ * and base[k] + the key's words rounded up to even <= base[k + 1] (n_words for
+ * the last key), so no run of set bits bridges two keys.  Keys whose status is
+ * not LC_SET_KEY_OK have no rows (add_off / read_off ranges are ignored).
+ * lc_set_check validates the offset arrays on the host; every id is checked
+ * against span[k] on the device, and a bad one ends the call with
+ * LC_E_INVALID naming the key.
+ */
+typedef struct lc_set_batch {
+    int64_t         n_keys;
+    const uint64_t *add_off;   /* [n_keys + 1] into add_id / add_cls           */
+    const uint32_t *add_id;
+    const uint8_t  *add_cls;   /* LC_SET_ATTEMPT / LC_SET_ACK                  */
+    const uint64_t *read_off;  /* [n_keys + 1] into read_id (the final read)   */
+    const uint32_t *read_id;
+    const uint64_t *base;      /* [n_keys] */
+    const uint32_t *span;      /* [n_keys] */
+    const int64_t  *min;       /* [n_keys] */
+    const uint8_t  *rank;      /* [n_keys] */
+    const uint64_t *vals_off;  /* [n_keys + 1] */
+    const int64_t  *vals;
+    const uint8_t  *status;    /* [n_keys] LC_SET_KEY_*, or NULL: all OK       */
+    uint64_t        n_words;   /* 64-bit words of one bitmap (even)            */
+} lc_set_batch;
+
+typedef struct lc_set_packed lc_set_packed;  /* library-owned */
+
+/* independent/checker's split by key (keys in order of first appearance; one
+ * key LC_NO_KEY when no row has one), then per key: the :invoke / :ok :add
+ * rows, the last :ok :read, element minimum and maximum, the id form
+ * (csrc/set_plan.hpp: plan_set_key) and the arrays above. */
+int  lc_set_pack(const lc_set_history *h, lc_set_packed **out);
+void lc_set_packed_free(lc_set_packed *p);
+int  lc_set_packed_view(const lc_set_packed *p, lc_set_batch *out);
+/* The independent key of every packed key (n_keys entries). */
+int  lc_set_packed_keys(const lc_set_packed *p, int64_t *out);
+/* Why key i is :unknown (NULL when it is not; borrowed). */
+const char *lc_set_packed_key_error(const lc_set_packed *p, int64_t i);
+
+/*
+ * jepsen.checker/set's result per key, caller-allocated:
+ *   counts   6 per key: attempt, acknowledged, ok, lost, recovered, unexpected
+ *   runs     the maximal runs of consecutive integers of each key's :ok, :lost,
+ *            :unexpected and :recovered sets (in that class order), as (first,
+ *            last) element values, ascending; class c of key k owns runs
+ *            run_off[4k + c] .. run_off[4k + c + 1)
+ * run_cap is the capacity of runs in runs (pairs); n_runs comes back.  When
+ * n_runs > run_cap the call returns LC_E_NOMEM, names the capacity needed in
+ * lc_last_error, sets n_runs to it and writes no runs.
+ */
+typedef struct lc_set_result {
+    int8_t   *valid;    /* [n_keys] LC_VALID / LC_INVALID / LC_UNKNOWN */
+    uint64_t *counts;   /* [6 * n_keys]     */
+    uint64_t *run_off;  /* [4 * n_keys + 1] */
+    int64_t  *runs;     /* [2 * run_cap]    */
+    uint64_t  run_cap;
+    uint64_t  n_runs;
+} lc_set_result;
+
+/* A run capacity that always suffices: acknowledged adds plus twice the read
+ * elements of the keys that are checked. */
+int64_t lc_set_batch_max_runs(const lc_set_batch *b);
+/* Check every key of the batch in one call on the context's stream (first
+ * device of the context): H2D, kernels, D2H. */
+int  lc_set_check(lc_ctx *ctx, const lc_set_batch *b, lc_set_result *r);
+/* Device-event times of the last lc_set_check, ms: [0] upload, [1] kernels,
+ * [2] download of the records, [3] the whole call (wall). */
+int  lc_set_last_timing(lc_ctx *ctx, double *out_ms);
+/* Launch constants of the set kernels (no device needed), in ids (bits):
+ * [0] one lane's chunk of k_set_classify (a 16-byte load), [1] a wave's,
+ * [2] a workgroup's, [3] the largest span the LDS tier takes, [4] the span up
+ * to which a key keeps offset ids whatever its row count, [5] rows per
+ * workgroup of k_set_mark, [6] the ids of its LDS tile. */
+int  lc_set_launch_info(int64_t *out7);
+
+/* history.edn of a set-workload run (:f :add with an integer :value, :f :read
+ * with nil or a #{...} / [...] / (...) of integers, optionally as [k v]
+ * tuples; every other op is LC_SF_OTHER with its value skipped).  A
+ * single-threaded read with lc_edn_parse's allocation-free reader. */
+typedef struct lc_set_hist lc_set_hist;  /* library-owned */
+int  lc_edn_read_set(const char *path, lc_set_hist **out);
+int  lc_edn_parse_set(const char *text, int64_t len, lc_set_hist **out);
+int  lc_set_hist_view(const lc_set_hist *h, lc_set_history *out);
+void lc_set_hist_free(lc_set_hist *h);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "device_search.hpp"
+#include "device_set.hpp"
 #include "step_plan.hpp"
 
 #define HIPCHK(expr)                                                                       \
@@ -339,9 +340,11 @@ struct Dev {
     } wws[2];
     uint32_t wgl_seq = 0;     // launches so far (the high half of every cache stamp)
     uint8_t *analyzer = nullptr;  // [cap_keys] LC_ALGO_* that answered each key
+    lcs::SetDev *setdev = nullptr;  // lc_set_check's cached arrays (device_set.hip), made on first use
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
+        lcs::set_dev_free(setdev);
         dfree(lists); dfree(ctl); dfree(valid); dfree(fail_event);
         if (hctl) (void)hipHostFree(hctl);
         dfree(cause); dfree(peak); dfree(final_cfg); dfree(n_final);
@@ -2274,4 +2277,20 @@ extern "C" int lc_node_records(lc_ctx *c, uint64_t *node, int64_t n) {
     if (n) HIPCHK(hipMemcpyAsync(node, d->node, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return LC_OK;
+}
+
+// ---- the set workload (set.clj:46; device_set.hip) ---------------------------
+
+extern "C" int lc_set_check(lc_ctx *c, const lc_set_batch *b, lc_set_result *r) {
+    if (!c || !b || !r) return lc::fail(LC_E_INVALID, "lc_set_check: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    Dev *d = c->dev[0];
+    HIPCHK(hipSetDevice(d->device));
+    return lcs::set_check(&d->setdev, d->stream, c->o.path_flags, b, r);
+}
+
+extern "C" int lc_set_last_timing(lc_ctx *c, double *out_ms) {
+    if (!c || !out_ms) return lc::fail(LC_E_INVALID, "lc_set_last_timing: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    return lcs::set_last_timing(c->dev[0]->setdev, out_ms);
 }

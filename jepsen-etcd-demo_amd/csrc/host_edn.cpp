@@ -725,3 +725,231 @@ extern "C" int lc_edn_write_named(const char *path, const lc_history *h, const c
     if (std::fclose(f) != 0) return lc::fail(LC_E_IO, "lc_edn_write: close failed");
     return LC_OK;
 }
+
+// ---- the set workload's history.edn (set.clj:25-35; ABI 12) -------------------
+// A second op handler over the same reader: :f :add / :read are the client
+// ops, an add's :value is an integer, a read's nil or a #{...} / [...] / (...)
+// of integers, either optionally inside an independent tuple [k v].  Tuples
+// are decided per history as above: every client op's value is a 2-vector
+// whose first element is an integer (and, for a read, whose second is not --
+// a plain read [1 2] of two elements is no tuple).  Single-threaded.
+
+struct lc_set_hist {
+    std::vector<uint8_t> type, f;
+    std::vector<int64_t> key, elem, read_off, read_elem, index;
+};
+
+namespace {
+
+struct SetRaw {
+    uint8_t type = 255, f = LC_SF_OTHER;
+    int64_t index = -1;
+    const char *vb = nullptr;  // the :value's text
+};
+
+bool read_set_op(Parser &ps, SetRaw &op) {
+    ++ps.p;  // at '{'
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated op map");
+        if (*ps.p == '}') { ++ps.p; break; }
+        std::string_view k;
+        bool is_kw = false;
+        if (!ps.keyword(k, is_kw)) return false;
+        if (!is_kw) {
+            if (!ps.skip()) return false;
+            continue;
+        }
+        const Field fld = field_of(k);
+        if (fld == FLD_TYPE || fld == FLD_F) {
+            std::string_view v;
+            bool vk = false;
+            if (!ps.keyword(v, vk)) return false;
+            if (fld == FLD_TYPE) {
+                if (!vk) return ps.fail(":type is not a keyword");
+                switch (pack8(v)) {
+                    case P8("invoke"): op.type = LC_INVOKE; break;
+                    case P8("ok"): op.type = LC_OK_T; break;
+                    case P8("fail"): op.type = LC_FAIL; break;
+                    case P8("info"): op.type = LC_INFO; break;
+                    default: return ps.fail("unknown :type :" + std::string(v));
+                }
+            } else {
+                op.f = !vk ? LC_SF_OTHER : pack8(v) == P8("add") ? LC_SF_ADD : pack8(v) == P8("read") ? LC_SF_READ : LC_SF_OTHER;
+            }
+        } else if (fld == FLD_INDEX) {
+            Leaf v;
+            if (!ps.shaped(v)) return false;
+            op.index = v.kind == K_INT ? v.i : -1;
+        } else if (fld == FLD_VALUE) {
+            if (!ps.prefixes()) return false;
+            op.vb = ps.p;
+            if (!ps.skip()) return false;
+        } else {
+            if (!ps.skip()) return false;
+        }
+    }
+    if (op.type == 255) return ps.fail("op map without :type");
+    return true;
+}
+
+// One element (or an add's value): an integer, else LC_NIL with the value skipped.
+bool set_element(Parser &ps, int64_t &out) {
+    out = LC_NIL;
+    if (!ps.prefixes()) return false;
+    const char c = *ps.p;
+    if (c == '[' || c == '(' || c == '{' || c == '"' || c == '\\' || c == ':' || c == '#') return ps.skip();
+    uint8_t kind;
+    int64_t v = 0;
+    if (!ps.scalar(kind, v)) return false;
+    if (kind == K_INT) out = v;
+    return true;
+}
+
+// A read's value from its text: nil (*is_nil), or a collection whose
+// elements are appended to out; anything else reads as one bad element.
+bool set_read_value(Parser &ps, bool &is_nil, std::vector<int64_t> &out) {
+    is_nil = false;
+    if (!ps.prefixes()) return false;
+    char close = 0;
+    if (*ps.p == '[') { close = ']'; ++ps.p; }
+    else if (*ps.p == '(') { close = ')'; ++ps.p; }
+    else if (*ps.p == '#' && ps.p + 1 < ps.end && ps.p[1] == '{') { close = '}'; ps.p += 2; }
+    if (!close) {
+        int64_t v;
+        const char *b = ps.p;
+        if (!set_element(ps, v)) return false;
+        if (std::string_view(b, (size_t)(ps.p - b)) == "nil") is_nil = true;
+        else out.push_back(LC_NIL);
+        return true;
+    }
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated collection");
+        if (*ps.p == close) { ++ps.p; return true; }
+        int64_t v;
+        if (!set_element(ps, v)) return false;
+        out.push_back(v);
+    }
+}
+
+int parse_set(const char *text, int64_t len, lc_set_hist **out) {
+    Parser ps{text, text + len, text};
+    std::vector<SetRaw> ops;
+    auto one = [&]() -> bool {
+        SetRaw op;
+        if (!read_set_op(ps, op)) return false;
+        ops.push_back(op);
+        return true;
+    };
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) break;
+        if (*ps.p == '{') {
+            if (!one()) break;
+        } else if (*ps.p == '[') {  // a vector of op maps
+            ++ps.p;
+            bool closed = false;
+            for (;;) {
+                ps.ws();
+                if (ps.p >= ps.end) { ps.fail("unterminated history vector"); break; }
+                if (*ps.p == ']') { ++ps.p; closed = true; break; }
+                if (*ps.p != '{') { ps.fail("expected an op map"); break; }
+                if (!one()) break;
+            }
+            if (!closed) break;
+        } else {
+            ps.fail("expected an op map");
+            break;
+        }
+    }
+    if (!ps.err.empty())
+        return lc::fail(LC_E_PARSE, "lc_edn_set: line %lld: %s", (long long)line_of(text, ps.err_off), ps.err.c_str());
+    // tuples?
+    bool indep = false, any_client = false;
+    for (const SetRaw &o : ops) {
+        if (o.f == LC_SF_OTHER) continue;
+        bool tup = false;
+        if (o.vb) {
+            Parser vp{o.vb, text + len, text};
+            Top v;
+            if (vp.shaped(v))
+                tup = v.kind == K_VEC && v.n == 2 && v.e[0].kind == K_INT && (o.f == LC_SF_ADD || v.e[1].kind != K_INT);
+        }
+        indep = any_client ? indep && tup : tup;
+        any_client = true;
+    }
+    auto *h = new lc_set_hist();
+    h->read_off.push_back(0);
+    for (size_t r = 0; r < ops.size(); ++r) {
+        const SetRaw &o = ops[r];
+        int64_t key = LC_NO_KEY, elem = 0;
+        if (o.f != LC_SF_OTHER) {
+            Parser vp{o.vb ? o.vb : "nil", o.vb ? text + len : nullptr, text};
+            if (!o.vb) vp.end = vp.p + 3;
+            bool ok = true;
+            if (indep) {
+                vp.ws();
+                ++vp.p;  // '[' of the tuple (checked above)
+                vp.ws();
+                uint8_t kind;
+                ok = vp.scalar(kind, key) && kind == K_INT;
+            }
+            if (ok && o.f == LC_SF_ADD) {
+                ok = set_element(vp, elem);
+            } else if (ok) {
+                bool is_nil = false;
+                ok = set_read_value(vp, is_nil, h->read_elem);
+                elem = is_nil ? LC_NIL : 0;
+            }
+            if (!ok) {
+                delete h;
+                return lc::fail(LC_E_PARSE, "lc_edn_set: op %lld: %s", (long long)r, vp.err.empty() ? "bad :value" : vp.err.c_str());
+            }
+        }
+        h->type.push_back(o.type); h->f.push_back(o.f); h->key.push_back(key); h->elem.push_back(elem);
+        h->index.push_back(o.index);
+        h->read_off.push_back((int64_t)h->read_elem.size());
+    }
+    *out = h;
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_edn_parse_set(const char *text, int64_t len, lc_set_hist **out) {
+    lc::Range range("lc_edn_parse_set");
+    if (!text || !out || len < 0) return lc::fail(LC_E_INVALID, "lc_edn_parse_set: null argument");
+    try {
+        return parse_set(text, len, out);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_edn_set: out of memory");
+    }
+}
+
+extern "C" int lc_edn_read_set(const char *path, lc_set_hist **out) {
+    if (!path || !out) return lc::fail(LC_E_INVALID, "lc_edn_read_set: null argument");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return lc::fail(LC_E_IO, "lc_edn_read_set: cannot open %s", path);
+    std::string s;
+    try {
+        char buf[1 << 16];
+        size_t r;
+        while ((r = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, r);
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return lc::fail(LC_E_NOMEM, "lc_edn_read_set: out of memory");
+    }
+    std::fclose(f);
+    return lc_edn_parse_set(s.data(), (int64_t)s.size(), out);
+}
+
+extern "C" int lc_set_hist_view(const lc_set_hist *h, lc_set_history *out) {
+    if (!h || !out) return lc::fail(LC_E_INVALID, "lc_set_hist_view: null argument");
+    out->n = (int64_t)h->type.size();
+    out->type = h->type.data(); out->f = h->f.data(); out->key = h->key.data(); out->elem = h->elem.data();
+    out->read_off = h->read_off.data(); out->read_elem = h->read_elem.data(); out->index = h->index.data();
+    return LC_OK;
+}
+
+extern "C" void lc_set_hist_free(lc_set_hist *h) { delete h; }

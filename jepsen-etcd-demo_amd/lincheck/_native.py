@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LINCHECK_LIB_OVERRIDE") or os.path.join(HERE, "liblincheck.so")  # override: diagnostics only
 
 # ---- constants (mirror include/lincheck.h) ---------------------------------
-LC_ABI_VERSION = 11
+LC_ABI_VERSION = 12
 LC_MAX_DEVICES = 8
 LC_COMM_ID_BYTES = 128
 LC_OPT_COUNT_PROBES = 0x1
@@ -27,6 +27,8 @@ LC_PATH_NODE_SYNC, LC_PATH_NODE_STAGED, LC_PATH_CHUNKS_ON, LC_PATH_CHUNKS_OFF = 
 LC_PATH_SPEC_COST, LC_PATH_EV32, LC_PATH_SPEC_NOPRIO, LC_PATH_WGL_SMALL = 0x100, 0x200, 0x400, 0x800
 LC_PATH_WGL_EV_HBM = 0x2000  # ABI 11
 LC_PATH_SPEC_NOSTAGE = 0x1000
+LC_PATH_SET_HBM = 0x4000  # ABI 12: lc_set_check, every key through the HBM tier
+LC_PATH_SET_DIRECT = 0x8000  # ABI 12: k_set_mark without its LDS tile
 LC_T0_PATH_NONE, LC_T0_PATH_LATTICE, LC_T0_PATH_SPEC, LC_T0_PATH_SEGMENTS = 0, 1, 2, 3
 T0_PATH_NAMES = {0: "none", 1: "k_search_lattice", 2: "k_spec", 3: "k_search_segments"}
 LC_DEV_RESULT, LC_DEV_ASYNC = 1, 2
@@ -109,6 +111,31 @@ class LcSynthOpts(C.Structure):
                 ("nemesis_period", C.c_double), ("seed", C.c_uint64), ("key_base", C.c_int64)]
 
 
+# ---- the set workload (ABI 12) ----------------------------------------------
+LC_SF_ADD, LC_SF_READ, LC_SF_OTHER = 0, 1, 2
+LC_SET_ATTEMPT, LC_SET_ACK = 1, 2
+LC_SET_KEY_OK, LC_SET_KEY_NEVER_READ, LC_SET_KEY_ERROR = 0, 1, 2
+
+
+class LcSetHistory(C.Structure):
+    _fields_ = [("n", C.c_int64), ("type", P(C.c_uint8)), ("f", P(C.c_uint8)), ("key", P(C.c_int64)),
+                ("elem", P(C.c_int64)), ("read_off", P(C.c_int64)), ("read_elem", P(C.c_int64)),
+                ("index", P(C.c_int64))]
+
+
+class LcSetBatch(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("add_off", P(C.c_uint64)), ("add_id", P(C.c_uint32)),
+                ("add_cls", P(C.c_uint8)), ("read_off", P(C.c_uint64)), ("read_id", P(C.c_uint32)),
+                ("base", P(C.c_uint64)), ("span", P(C.c_uint32)), ("min", P(C.c_int64)), ("rank", P(C.c_uint8)),
+                ("vals_off", P(C.c_uint64)), ("vals", P(C.c_int64)), ("status", P(C.c_uint8)),
+                ("n_words", C.c_uint64)]
+
+
+class LcSetResult(C.Structure):
+    _fields_ = [("valid", P(C.c_int8)), ("counts", P(C.c_uint64)), ("run_off", P(C.c_uint64)),
+                ("runs", P(C.c_int64)), ("run_cap", C.c_uint64), ("n_runs", C.c_uint64)]
+
+
 # Every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
 # this table against include/lincheck.h.
 SIGNATURES = {
@@ -160,6 +187,19 @@ SIGNATURES = {
     "lc_fressian_read": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
     "lc_fressian_parse": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
     "lc_fressian_write": (C.c_int, [C.c_char_p, P(LcHistory)]),
+    "lc_set_pack": (C.c_int, [P(LcSetHistory), P(C.c_void_p)]),
+    "lc_set_packed_free": (None, [C.c_void_p]),
+    "lc_set_packed_view": (C.c_int, [C.c_void_p, P(LcSetBatch)]),
+    "lc_set_packed_keys": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_set_packed_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_set_batch_max_runs": (C.c_int64, [P(LcSetBatch)]),
+    "lc_set_check": (C.c_int, [C.c_void_p, P(LcSetBatch), P(LcSetResult)]),
+    "lc_set_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_set_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_edn_read_set": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+    "lc_edn_parse_set": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
+    "lc_set_hist_view": (C.c_int, [C.c_void_p, P(LcSetHistory)]),
+    "lc_set_hist_free": (None, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -8,6 +8,9 @@
          "analyzer": "linear"} with :configs / :final-paths truncated to 10.
     compose({name: checker}) / merge_valid / check_safe
         jepsen.checker/compose, merge-valid, check-safe.
+    set_() (alias: set)
+        jepsen.checker/set (set.clj:46), the set workload's checker:
+        lincheck.setcheck.
 
 Under independent.checker the linearizable check is batched: every key goes
 to the device in one call (Batch below).  Device failures raise; check_safe
@@ -720,6 +723,28 @@ def check_safe(checker, test, history, opts=None) -> Dict:
         return checker.check(test, history, opts or {})
     except Exception as e:  # noqa: BLE001 -- mirrors check-safe catching Throwable
         return {"valid?": "unknown", "error": "".join(traceback.format_exception_only(type(e), e)).strip()}
+
+
+def set_(opts: Optional[Dict] = None):
+    """jepsen.checker/set (set.clj:46).  `set` shadows the builtin; both names
+    are exported, as independent.tuple_ / tuple are."""
+    from .setcheck import SetChecker
+    return SetChecker(opts)
+
+
+globals()["set"] = set_
+
+
+def batched_set(inner):
+    """The SetChecker inside `inner` if independent.checker can batch it."""
+    from .setcheck import SetChecker
+    if isinstance(inner, SetChecker):
+        return inner
+    if isinstance(inner, Compose):
+        sets = [c for c in inner.checkers.values() if isinstance(c, SetChecker)]
+        if len(sets) == 1 and not any(isinstance(c, Linearizable) for c in inner.checkers.values()):
+            return sets[0]
+    return None
 
 
 def batched_linearizable(inner) -> Optional[Linearizable]:

@@ -9,6 +9,8 @@ key, runs `inner` on every key's sub-history and merges the results as
 When `inner` is (a compose of) lincheck.checker.linearizable, the whole
 history goes to the device in ONE batched call (lc_pack + lc_check_batch)
 instead of one search per key: that is the drop-in this repository exists for.
+A (compose holding a) lincheck.checker.set_ is batched the same way: every
+key's set in one lc_set_check call.
 """
 
 from __future__ import annotations
@@ -80,6 +82,9 @@ class IndependentChecker:
         from . import checker as ck
         opts = dict(opts or {})
         batched = ck.batched_linearizable(self.inner)
+        if batched is not None:
+            return batched.check_independent(test, history, opts, self.inner)
+        batched = ck.batched_set(self.inner)
         if batched is not None:
             return batched.check_independent(test, history, opts, self.inner)
         results = {}
