@@ -43,7 +43,7 @@
 extern "C" {
 #endif
 
-#define LC_ABI_VERSION 12
+#define LC_ABI_VERSION 13
 
 /* ---- error codes --------------------------------------------------------- */
 #define LC_OK            0
@@ -758,6 +758,132 @@ int  lc_edn_read_set(const char *path, lc_set_hist **out);
 int  lc_edn_parse_set(const char *text, int64_t len, lc_set_hist **out);
 int  lc_set_hist_view(const lc_set_hist *h, lc_set_history *out);
 void lc_set_hist_free(lc_set_hist *h);
+
+/* ---- checker/perf (etcdemo.clj:165-167, ABI 13) -------------------------------- */
+/* The demo's check phase is (checker/compose {:perf (checker/perf) :indep ...}).
+ * This path computes what jepsen.checker.perf computes before it draws: the
+ * latency of every completed client op, latency quantiles per (:f, window)
+ * and completion counts per (:f, :type, window).  Restated from the public
+ * Jepsen 0.2.x source of jepsen.checker.perf and jepsen.util/history->latencies
+ * (parity unpinned).  Its own structs and entry points;
+ * nothing above changes. */
+#define LC_PERF_MAX_F 32          /* distinct :f names in one history            */
+#define LC_PERF_MAX_Q 8           /* quantiles in one call                       */
+#define LC_PERF_NO_INVOKE INT64_MIN  /* t_inv of a completion without an invocation */
+#define LC_PERF_META(f_inv, f_comp, type) ((uint32_t)(f_inv) | (uint32_t)(f_comp) << 8 | (uint32_t)(type) << 16)
+/* lc_perf_opts.flags: path switches for tests and A/B runs */
+#define LC_PERF_SELECT_HBM   0x1  /* every non-empty group through the HBM select */
+#define LC_PERF_COUNT_DIRECT 0x2  /* k_perf_count / k_perf_scatter without their LDS
+                                     tile: one global atomic per record            */
+
+/*
+ * A whole (unsplit) history as struct-of-arrays, one row per op map, in
+ * history order.  Times need not be monotone.
+ *   f        an id below n_f into a table of :f names the caller owns
+ *   process  the client's integer :process, or LC_NO_PROCESS (:nemesis ...)
+ *   time     the op's :time, integer nanoseconds
+ *   f_start / f_stop  the ids of :start and :stop (nemesis intervals), or -1
+ */
+typedef struct lc_perf_history {
+    int64_t        n;
+    const uint8_t *type;     /* LC_INVOKE / LC_OK_T / LC_FAIL / LC_INFO */
+    const uint8_t *f;
+    const int64_t *process;
+    const int64_t *time;
+    int32_t        n_f;
+    int32_t        f_start;
+    int32_t        f_stop;
+} lc_perf_history;
+
+/*
+ * lc_perf_pack's output, or caller-built: one record per client completion
+ * (every client row that is no :invoke), in history order.
+ *   meta    LC_PERF_META(f_inv, f_comp, type): the :f of the invocation the row
+ *           completes (its own for an orphan), its own :f, its own :type
+ *   t_comp  its own :time
+ *   t_inv   the invocation's :time, or LC_PERF_NO_INVOKE for an orphan
+ * t_min / t_max bound t_comp over all records, x_min / x_max bound t_inv over
+ * the matched ones (ignored when there is none).  The device checks every
+ * record against them before it addresses a table; a record outside ends the
+ * call with LC_E_INVALID.
+ */
+typedef struct lc_perf_batch {
+    int64_t         n;
+    const int64_t  *t_comp;
+    const int64_t  *t_inv;
+    const uint32_t *meta;
+    int64_t         n_matched;
+    int64_t         t_min, t_max;
+    int64_t         x_min, x_max;
+    int32_t         n_f;
+    int32_t         reserved;
+} lc_perf_batch;
+
+typedef struct lc_perf_packed lc_perf_packed;  /* library-owned */
+
+/* Pairing, orphans and nemesis intervals in one O(n) pass over the rows.
+ * More than LC_PERF_MAX_F names: LC_E_UNSUPPORTED.  A :type above LC_INFO or
+ * an f at or above n_f: LC_E_INVALID. */
+int  lc_perf_pack(const lc_perf_history *h, lc_perf_packed **out);
+void lc_perf_packed_free(lc_perf_packed *p);
+int  lc_perf_packed_view(const lc_perf_packed *p, lc_perf_batch *out);
+/* out4: matched pairs, unmatched invocations, orphans, nemesis intervals. */
+int  lc_perf_packed_info(const lc_perf_packed *p, int64_t *out4);
+/* The nemesis intervals as (t0, t1) pairs: 2 * out4[3] values. */
+int  lc_perf_packed_intervals(const lc_perf_packed *p, int64_t *out);
+
+typedef struct lc_perf_opts {
+    int64_t  quantile_dt_ns;       /* 30 s */
+    int64_t  rate_dt_ns;           /* 10 s */
+    int32_t  n_q;                  /* 1 .. LC_PERF_MAX_Q */
+    uint32_t flags;                /* LC_PERF_* */
+    double   q[LC_PERF_MAX_Q];     /* 0.5 0.95 0.99 1 */
+} lc_perf_opts;
+void lc_perf_opts_default(lc_perf_opts *o);
+
+/*
+ * The series, caller-allocated (lc_perf_shape gives the sizes):
+ *   rate    [n_f][3][rate_n] completions of (:f, :ok / :fail / :info, bucket
+ *           rate_first + i), by each row's own :f, :type and :time
+ *   group   [n_f][q_n] latency points of (:f, bucket q_first + i)
+ *   quant   [n_f][q_n][n_q] the latency at index
+ *           min(n - 1, (long) floor((double) n * q)) of the group's points in
+ *           ascending (invocation time, latency) order; meaningful where the
+ *           group count is above 0
+ * rate_cap / group_cap / quant_cap are the arrays' capacities in elements.
+ */
+typedef struct lc_perf_result {
+    uint64_t *rate;
+    uint64_t *group;
+    int64_t  *quant;
+    uint64_t  rate_cap, group_cap, quant_cap;
+    int64_t   rate_first, rate_n;
+    int64_t   q_first, q_n;
+} lc_perf_result;
+
+/* out4: rate_first, rate_n, q_first, q_n of a batch under opts (no device
+ * needed); a width that is not positive: LC_E_INVALID. */
+int  lc_perf_shape(const lc_perf_batch *b, const lc_perf_opts *o, int64_t *out4);
+/* One call on the context's stream (first device): H2D, kernels, D2H. */
+int  lc_perf_check(lc_ctx *ctx, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r);
+/* Device-event times of the last lc_perf_check, ms: [0] upload, [1] kernels,
+ * [2] download, [3] the whole call (wall). */
+int  lc_perf_last_timing(lc_ctx *ctx, double *out_ms);
+/* Launch constants (no device needed): [0] records per workgroup of the
+ * streaming kernels, [1] buckets the LDS histogram tile spans, [2] the largest
+ * group the LDS select takes, [3] bits per digit of the HBM select. */
+int  lc_perf_launch_info(int64_t *out4);
+
+/* history.edn for perf: :type :f :process :time of every op map, every
+ * :value skipped; :f names interned in order of first appearance.  A
+ * single-threaded read with lc_edn_parse's allocation-free reader. */
+typedef struct lc_perf_hist lc_perf_hist;  /* library-owned */
+int  lc_edn_read_perf(const char *path, lc_perf_hist **out);
+int  lc_edn_parse_perf(const char *text, int64_t len, lc_perf_hist **out);
+int  lc_perf_hist_view(const lc_perf_hist *h, lc_perf_history *out);
+/* Name i of the view's n_f names (borrowed; NULL out of range). */
+const char *lc_perf_hist_name(const lc_perf_hist *h, int64_t i);
+void lc_perf_hist_free(lc_perf_hist *h);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,7 @@
 
 #include "common.hpp"
 #include "device_search.hpp"
+#include "device_perf.hpp"
 #include "device_set.hpp"
 #include "step_plan.hpp"
 
@@ -341,10 +342,12 @@ struct Dev {
     uint32_t wgl_seq = 0;     // launches so far (the high half of every cache stamp)
     uint8_t *analyzer = nullptr;  // [cap_keys] LC_ALGO_* that answered each key
     lcs::SetDev *setdev = nullptr;  // lc_set_check's cached arrays (device_set.hip), made on first use
+    lcp::PerfDev *perfdev = nullptr;  // lc_perf_check's (device_perf.hip), likewise
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         lcs::set_dev_free(setdev);
+        lcp::perf_dev_free(perfdev);
         dfree(lists); dfree(ctl); dfree(valid); dfree(fail_event);
         if (hctl) (void)hipHostFree(hctl);
         dfree(cause); dfree(peak); dfree(final_cfg); dfree(n_final);
@@ -2293,4 +2296,20 @@ extern "C" int lc_set_last_timing(lc_ctx *c, double *out_ms) {
     if (!c || !out_ms) return lc::fail(LC_E_INVALID, "lc_set_last_timing: null argument");
     std::lock_guard<std::mutex> g(c->mu);
     return lcs::set_last_timing(c->dev[0]->setdev, out_ms);
+}
+
+// ---- checker/perf (etcdemo.clj:165-167; device_perf.hip) ----------------------
+
+extern "C" int lc_perf_check(lc_ctx *c, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r) {
+    if (!c || !b || !o || !r) return lc::fail(LC_E_INVALID, "lc_perf_check: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    Dev *d = c->dev[0];
+    HIPCHK(hipSetDevice(d->device));
+    return lcp::perf_check(&d->perfdev, d->stream, b, o, r);
+}
+
+extern "C" int lc_perf_last_timing(lc_ctx *c, double *out_ms) {
+    if (!c || !out_ms) return lc::fail(LC_E_INVALID, "lc_perf_last_timing: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    return lcp::perf_last_timing(c->dev[0]->perfdev, out_ms);
 }

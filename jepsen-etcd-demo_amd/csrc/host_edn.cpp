@@ -953,3 +953,181 @@ extern "C" int lc_set_hist_view(const lc_set_hist *h, lc_set_history *out) {
 }
 
 extern "C" void lc_set_hist_free(lc_set_hist *h) { delete h; }
+
+// ---- history.edn for checker/perf (ABI 13) -------------------------------------
+// A third op handler over the same reader: :type, :f, :process and :time of
+// every op map, every :value skipped.  :f names (any keyword; another kind of
+// value reads as its text) are interned in order of first appearance; an op
+// map without :f gets the name "nil".  A map without an integer :time is a
+// parse error: no latency can be computed from it.  Single-threaded.
+
+struct lc_perf_hist {
+    std::vector<uint8_t> type, f;
+    std::vector<int64_t> process, time;
+    std::vector<std::string> names;
+};
+
+namespace {
+
+struct PerfNames {
+    std::unordered_map<std::string, uint32_t> id;
+    std::vector<std::string> *names;
+    std::string_view last;  // the last name looked up (most ops repeat it)
+    uint32_t last_id = 0;
+    uint32_t of(std::string_view t) {
+        if (!last.empty() && t == last) return last_id;
+        auto it = id.find(std::string(t));
+        if (it == id.end()) {
+            names->emplace_back(t);
+            it = id.emplace(names->back(), (uint32_t)names->size() - 1).first;
+        }
+        last = it->first;
+        last_id = it->second;
+        return last_id;
+    }
+};
+
+bool read_perf_op(Parser &ps, PerfNames &names, lc_perf_hist &h) {
+    ++ps.p;  // at '{'
+    uint8_t type = 255;
+    int64_t process = LC_NO_PROCESS, time = 0;
+    bool have_time = false;
+    std::string_view fname = "nil";
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated op map");
+        if (*ps.p == '}') { ++ps.p; break; }
+        std::string_view k;
+        bool is_kw = false;
+        if (!ps.keyword(k, is_kw)) return false;
+        if (!is_kw) {
+            if (!ps.skip()) return false;
+            continue;
+        }
+        const uint64_t k8 = pack8(k);
+        if (k8 == P8("type")) {
+            std::string_view v;
+            bool vk = false;
+            if (!ps.keyword(v, vk)) return false;
+            if (!vk) return ps.fail(":type is not a keyword");
+            switch (pack8(v)) {
+                case P8("invoke"): type = LC_INVOKE; break;
+                case P8("ok"): type = LC_OK_T; break;
+                case P8("fail"): type = LC_FAIL; break;
+                case P8("info"): type = LC_INFO; break;
+                default: return ps.fail("unknown :type :" + std::string(v));
+            }
+        } else if (k8 == P8("f")) {
+            if (!ps.prefixes()) return false;
+            const char *b = ps.p;
+            if (*ps.p == ':') {
+                bool vk = false;
+                if (!ps.keyword(fname, vk)) return false;
+            } else {
+                if (!ps.skip()) return false;
+                fname = std::string_view(b, (size_t)(ps.p - b));
+            }
+        } else if (k8 == P8("process") || k8 == P8("time")) {
+            Leaf v;
+            if (!ps.shaped(v)) return false;
+            if (k8 == P8("process")) {
+                process = v.kind == K_INT ? v.i : LC_NO_PROCESS;
+            } else {
+                if (v.kind != K_INT) return ps.fail(":time is not an integer");
+                time = v.i;
+                have_time = true;
+            }
+        } else {
+            if (!ps.skip()) return false;
+        }
+    }
+    if (type == 255) return ps.fail("op map without :type");
+    if (!have_time) return ps.fail("op map without :time");
+    const uint32_t f = names.of(fname);
+    if (f > 255) return ps.fail("more than 256 distinct :f");
+    h.type.push_back(type); h.f.push_back((uint8_t)f); h.process.push_back(process); h.time.push_back(time);
+    return true;
+}
+
+int parse_perf(const char *text, int64_t len, lc_perf_hist **out) {
+    Parser ps{text, text + len, text};
+    auto *h = new lc_perf_hist();
+    PerfNames names;
+    names.names = &h->names;
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) break;
+        if (*ps.p == '{') {
+            if (!read_perf_op(ps, names, *h)) break;
+        } else if (*ps.p == '[') {  // a vector of op maps
+            ++ps.p;
+            bool closed = false;
+            for (;;) {
+                ps.ws();
+                if (ps.p >= ps.end) { ps.fail("unterminated history vector"); break; }
+                if (*ps.p == ']') { ++ps.p; closed = true; break; }
+                if (*ps.p != '{') { ps.fail("expected an op map"); break; }
+                if (!read_perf_op(ps, names, *h)) break;
+            }
+            if (!closed) break;
+        } else {
+            ps.fail("expected an op map");
+            break;
+        }
+    }
+    if (!ps.err.empty()) {
+        delete h;
+        return lc::fail(LC_E_PARSE, "lc_edn_perf: line %lld: %s", (long long)line_of(text, ps.err_off), ps.err.c_str());
+    }
+    *out = h;
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_edn_parse_perf(const char *text, int64_t len, lc_perf_hist **out) {
+    lc::Range range("lc_edn_parse_perf");
+    if (!text || !out || len < 0) return lc::fail(LC_E_INVALID, "lc_edn_parse_perf: null argument");
+    try {
+        return parse_perf(text, len, out);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_edn_perf: out of memory");
+    }
+}
+
+extern "C" int lc_edn_read_perf(const char *path, lc_perf_hist **out) {
+    if (!path || !out) return lc::fail(LC_E_INVALID, "lc_edn_read_perf: null argument");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return lc::fail(LC_E_IO, "lc_edn_read_perf: cannot open %s", path);
+    std::string s;
+    try {
+        char buf[1 << 16];
+        size_t r;
+        while ((r = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, r);
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return lc::fail(LC_E_NOMEM, "lc_edn_read_perf: out of memory");
+    }
+    std::fclose(f);
+    return lc_edn_parse_perf(s.data(), (int64_t)s.size(), out);
+}
+
+extern "C" int lc_perf_hist_view(const lc_perf_hist *h, lc_perf_history *out) {
+    if (!h || !out) return lc::fail(LC_E_INVALID, "lc_perf_hist_view: null argument");
+    out->n = (int64_t)h->type.size();
+    out->type = h->type.data(); out->f = h->f.data(); out->process = h->process.data(); out->time = h->time.data();
+    out->n_f = (int32_t)h->names.size();
+    out->f_start = out->f_stop = -1;
+    for (size_t i = 0; i < h->names.size(); ++i) {
+        if (h->names[i] == "start") out->f_start = (int32_t)i;
+        if (h->names[i] == "stop") out->f_stop = (int32_t)i;
+    }
+    return LC_OK;
+}
+
+extern "C" const char *lc_perf_hist_name(const lc_perf_hist *h, int64_t i) {
+    if (!h || i < 0 || (size_t)i >= h->names.size()) return nullptr;
+    return h->names[(size_t)i].c_str();
+}
+
+extern "C" void lc_perf_hist_free(lc_perf_hist *h) { delete h; }

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LINCHECK_LIB_OVERRIDE") or os.path.join(HERE, "liblincheck.so")  # override: diagnostics only
 
 # ---- constants (mirror include/lincheck.h) ---------------------------------
-LC_ABI_VERSION = 12
+LC_ABI_VERSION = 13
 LC_MAX_DEVICES = 8
 LC_COMM_ID_BYTES = 128
 LC_OPT_COUNT_PROBES = 0x1
@@ -136,6 +136,34 @@ class LcSetResult(C.Structure):
                 ("runs", P(C.c_int64)), ("run_cap", C.c_uint64), ("n_runs", C.c_uint64)]
 
 
+# ---- checker/perf (ABI 13) ---------------------------------------------------
+LC_PERF_MAX_F, LC_PERF_MAX_Q = 32, 8
+LC_PERF_NO_INVOKE = LC_NIL
+LC_PERF_SELECT_HBM, LC_PERF_COUNT_DIRECT = 0x1, 0x2  # lc_perf_opts.flags
+
+
+class LcPerfHistory(C.Structure):
+    _fields_ = [("n", C.c_int64), ("type", P(C.c_uint8)), ("f", P(C.c_uint8)), ("process", P(C.c_int64)),
+                ("time", P(C.c_int64)), ("n_f", C.c_int32), ("f_start", C.c_int32), ("f_stop", C.c_int32)]
+
+
+class LcPerfBatch(C.Structure):
+    _fields_ = [("n", C.c_int64), ("t_comp", P(C.c_int64)), ("t_inv", P(C.c_int64)), ("meta", P(C.c_uint32)),
+                ("n_matched", C.c_int64), ("t_min", C.c_int64), ("t_max", C.c_int64), ("x_min", C.c_int64),
+                ("x_max", C.c_int64), ("n_f", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LcPerfOpts(C.Structure):
+    _fields_ = [("quantile_dt_ns", C.c_int64), ("rate_dt_ns", C.c_int64), ("n_q", C.c_int32), ("flags", C.c_uint32),
+                ("q", C.c_double * LC_PERF_MAX_Q)]
+
+
+class LcPerfResult(C.Structure):
+    _fields_ = [("rate", P(C.c_uint64)), ("group", P(C.c_uint64)), ("quant", P(C.c_int64)),
+                ("rate_cap", C.c_uint64), ("group_cap", C.c_uint64), ("quant_cap", C.c_uint64),
+                ("rate_first", C.c_int64), ("rate_n", C.c_int64), ("q_first", C.c_int64), ("q_n", C.c_int64)]
+
+
 # Every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
 # this table against include/lincheck.h.
 SIGNATURES = {
@@ -200,6 +228,21 @@ SIGNATURES = {
     "lc_edn_parse_set": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
     "lc_set_hist_view": (C.c_int, [C.c_void_p, P(LcSetHistory)]),
     "lc_set_hist_free": (None, [C.c_void_p]),
+    "lc_perf_pack": (C.c_int, [P(LcPerfHistory), P(C.c_void_p)]),
+    "lc_perf_packed_free": (None, [C.c_void_p]),
+    "lc_perf_packed_view": (C.c_int, [C.c_void_p, P(LcPerfBatch)]),
+    "lc_perf_packed_info": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_perf_packed_intervals": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_perf_opts_default": (None, [P(LcPerfOpts)]),
+    "lc_perf_shape": (C.c_int, [P(LcPerfBatch), P(LcPerfOpts), P(C.c_int64)]),
+    "lc_perf_check": (C.c_int, [C.c_void_p, P(LcPerfBatch), P(LcPerfOpts), P(LcPerfResult)]),
+    "lc_perf_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_perf_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_edn_read_perf": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+    "lc_edn_parse_perf": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
+    "lc_perf_hist_view": (C.c_int, [C.c_void_p, P(LcPerfHistory)]),
+    "lc_perf_hist_name": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_perf_hist_free": (None, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -11,6 +11,9 @@
     set_() (alias: set)
         jepsen.checker/set (set.clj:46), the set workload's checker:
         lincheck.setcheck.
+    perf()
+        jepsen.checker/perf (etcdemo.clj:166): always valid; the latency and
+        rate series computed on the device: lincheck.perf.
 
 Under independent.checker the linearizable check is batched: every key goes
 to the device in one call (Batch below).  Device failures raise; check_safe
@@ -733,6 +736,13 @@ def set_(opts: Optional[Dict] = None):
 
 
 globals()["set"] = set_
+
+
+def perf(opts: Optional[Dict] = None):
+    """jepsen.checker/perf (etcdemo.clj:166): {"valid?": True}; the series it
+    would plot are computed on the device (lincheck.perf)."""
+    from .perf import PerfChecker
+    return PerfChecker(opts)
 
 
 def batched_set(inner):
