@@ -1,0 +1,619 @@
+"""cas-register histories built to a schedule, for the register tier's edges.
+
+`histgen.random_history` completes reads with random values, so its keys die
+within a few dozen events, and `lincheck.history.synth` cannot hold a chosen
+pending count at a chosen place.  Here a key follows a per-key schedule --
+"invoke" / "complete the op in position i of the pending list" -- and is
+linearizable by construction: every op takes effect at one instant inside its
+interval, applied there to a ground-truth register; a read returns what it
+saw, a cas is drawn so that it succeeds.  Directed anomalies (a read of a
+value no op writes, a read of a value a completed write had overwritten) are
+placed by event position.
+
+Profiles are pending-count sequences (`counts`): c[b] is the number of ops
+pending at boundary b (before event b), b = 0 .. nev.  Every event changes
+the count by one, so c[b] has the parity of b: a dip to d can only lie at a
+boundary of d's parity (`dip_boundary` moves it one boundary later when the
+parities differ).
+
+The constants below restate the kernels' (jepsen-etcd-demo_amd/csrc).  They
+serve only to place cases and to assert preconditions on the inputs; expected
+results always come from the oracle."""
+from __future__ import annotations
+
+import random
+from dataclasses import dataclass, field
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+
+from lincheck import history as H
+from lincheck.checker import Packed
+from lincheck.independent import Tuple
+
+SPEC_MIN_LEN = 128            # device_lattice.hip:1708 SPEC_MIN_LEN (events per segment at least)
+SPEC_MAX_PEND = 6             # device_lattice.hip:1709 SPEC_MAX_PEND (ops pending at a cut at most)
+SPEC_CUT_WINDOW = 64          # device_lattice.hip:1846-1863 spec_cut_at (boundaries t .. t + 64)
+SPEC_EV_LDS = (3072, 4096)    # device_lattice.hip:2325 spec_ev_lds() (event words staged in LDS)
+SPEC_CK_DEFAULT = (32, 120)   # device_api.hip:1450-1451 (default checkpoint distances past a cut)
+T0_MAX_WIDTH = 10             # device_lattice.hip:62 LC_T0_MAX_WIDTH
+T0_MAX_STATES = 32            # device_lattice.hip:65 T0_MAX_STATES
+TAGGABLE_MAX_STATES = 6       # device_api.hip:817 (taggable: shared table, states 0..5)
+
+
+def spec_eff(nev: int, S: int) -> int:
+    """Segments of a key of nev events on S waves (device_lattice.hip:2419-2420)."""
+    return 1 if nev < 2 * SPEC_MIN_LEN else min(S, nev // SPEC_MIN_LEN)
+
+
+def spec_targets(nev: int, S: int) -> List[int]:
+    """Equal-count targets 1 .. eff - 1 (device_lattice.hip:2495)."""
+    eff = spec_eff(nev, S)
+    return [nev * s // eff for s in range(1, eff)]
+
+
+def cut_window(t: int) -> range:
+    """The boundaries searched for target t's cut (spec_cut_at)."""
+    return range(t, t + SPEC_CUT_WINDOW + 1)
+
+
+def spec_cut(c: Sequence[int], nev: int, t: int) -> Optional[int]:
+    """spec_cut_at on a pending-count sequence: of the boundaries t .. t + 64
+    inside the key (boundary t: t < nev; boundary j + 1: j + 1 < nev), the
+    earliest with the fewest ops pending, if that is at most SPEC_MAX_PEND."""
+    best = None
+    for b in cut_window(t):
+        if b >= nev:
+            break
+        if c[b] <= SPEC_MAX_PEND and (best is None or c[b] < c[best]):
+            best = b
+    return best
+
+
+def spec_cuts(c: Sequence[int], nev: int, S: int) -> List[Optional[int]]:
+    """The kept cuts of segments 1 .. eff - 1 (device_lattice.hip:2524-2532):
+    a cut at or before the last kept one is dropped."""
+    out, last = [], 0
+    for t in spec_targets(nev, S):
+        cut = spec_cut(c, nev, t)
+        if cut is not None and cut <= last:
+            cut = None
+        if cut is not None:
+            last = cut
+        out.append(cut)
+    return out
+
+
+SPEC_W_EV, SPEC_W_MID, SPEC_W_HEAVY = 8, 2, 240  # device_lattice.hip:1749 (an event, an :ok at 7-8, at 9-10 pending)
+
+
+def spec_targets_cost(c: Sequence[int], nev: int, S: int) -> List[int]:
+    """LC_PATH_SPEC_COST's targets (device_lattice.hip:1784 spec_targets_cost):
+    target s is the first event up to and including which the key has s / eff
+    of its estimated cost."""
+    eff = spec_eff(nev, S)
+    cost = []
+    for b in range(nev):
+        ok = c[b + 1] < c[b]
+        cost.append(SPEC_W_EV + (SPEC_W_MID if ok and 7 <= c[b] <= 8 else 0) + (SPEC_W_HEAVY if ok and c[b] >= 9 else 0))
+    total, acc, out, nxt = sum(cost), 0, [], 1
+    for b in range(nev):
+        acc += cost[b]
+        while nxt < eff and acc >= total * nxt // eff:
+            out.append(b)
+            nxt += 1
+    return out
+
+
+# ---------------------------------------------------------------- profiles
+def dip_boundary(at: int, d: int) -> int:
+    """The boundary a dip to d asked for at `at` lies at: `at`, or the next
+    one when d and `at` differ in parity (c[b] has b's parity)."""
+    return at if (at - d) % 2 == 0 else at + 1
+
+
+def counts(nev: int, hi: int, dips=(), bumps=(), plateaus=(), drain: bool = False, stuck: int = 0,
+           wide: bool = False) -> List[int]:
+    """c[0 .. nev]: a ramp from 0, then the band {hi - 1, hi} (the member of
+    b's parity; wide: hi, hi - 1, hi - 2, hi - 1, so that :oks come at hi and
+    at hi - 1 pending), lowered to d + |b - at| around each dip (at, d), raised to
+    p - |b - at| around each bump (at, p) and to the band {p - 1, p} over
+    each plateau (from, to, p); drain: down to `stuck` ops (or one more, by
+    parity) at the end."""
+    for at, d in list(dips) + list(bumps) + [(a, p) for a, _e, p in plateaus] + [(e, p) for _a, e, p in plateaus]:
+        if (at - d) % 2:
+            raise ValueError(f"boundary {at} cannot have {d} ops pending (parity)")
+    r = stuck if (nev + stuck) % 2 == 0 else stuck + 1
+    c = []
+    for b in range(nev + 1):
+        v = hi if (b - hi) % 2 == 0 else hi - 1
+        if wide and (b - hi) % 4 == 2:
+            v = hi - 2
+        for at, p in bumps:
+            v = max(v, p - abs(b - at))
+        for a, e, p in plateaus:
+            v = max(v, min(p if (b - p) % 2 == 0 else p - 1, p - max(a - b, b - e, 0)))
+        for at, d in dips:
+            v = min(v, d + abs(b - at))
+        v = min(v, b)
+        if drain:
+            v = min(v, nev - b + r)
+        c.append(v)
+    assert all(abs(c[b + 1] - c[b]) == 1 for b in range(nev)), "not a pending-count sequence"
+    return c
+
+
+@dataclass
+class Plan:
+    """One key: its pending counts and what is directed in it."""
+    nev: int
+    c: List[int]
+    hold: Dict[int, int] = field(default_factory=dict)    # invoke ordinal -> the event that completes it
+    crash: Dict[int, int] = field(default_factory=dict)   # invoke ordinal -> :info once this many events exist
+    kinds: Dict[int, str] = field(default_factory=dict)   # invoke ordinal -> f
+    apply_at: Dict[int, int] = field(default_factory=dict)  # invoke ordinal -> takes effect before this event
+    anomalies: List[tuple] = field(default_factory=list)  # (position, "garbage" | "stale")
+    fail_pairs: int = 0                                   # leading invoke / :fail pairs (no events)
+    distinct: Dict[int, int] = field(default_factory=dict)  # invoke ordinal -> which of the values it writes
+
+    def with_anomalies(self, *anoms) -> "Plan":
+        """(pos, kind): the first :ok at or past event pos is a read of a bad value."""
+        p = Plan(self.nev, self.c, dict(self.hold), dict(self.crash), dict(self.kinds), dict(self.apply_at),
+                 list(anoms), self.fail_pairs, dict(self.distinct))
+        return p
+
+    def ok_events(self) -> List[int]:
+        return [b for b in range(self.nev) if self.c[b + 1] < self.c[b]]
+
+    def first_ok_at(self, pos: int) -> int:
+        return next(b for b in range(max(pos, 0), self.nev) if self.c[b + 1] < self.c[b])
+
+
+def rolling(nev: int, P: int, first: str = "complete") -> Plan:
+    """P ops pending throughout after warm-up.  first="complete": complete
+    one, invoke one (counts P, P - 1); first="invoke": invoke one, complete
+    one (counts P, P + 1).  The ops left at the end never return."""
+    return Plan(nev, counts(nev, P if first == "complete" else P + 1))
+
+
+def dips(nev: int, floor: int, dip_to: int, where: Sequence[int], drain: bool = True, wide: bool = False) -> Plan:
+    """`floor` ops pending (counts floor, floor - 1; wide: floor - 2 too),
+    falling to dip_to at the boundaries `where` (each at dip_boundary(at, dip_to))."""
+    return Plan(nev, counts(nev, floor, [(dip_boundary(at, dip_to), dip_to) for at in where], drain=drain, wide=wide))
+
+
+def quiescent_at(nev: int, positions: Sequence[int], floor: int = 5) -> Plan:
+    """Nothing pending at the boundaries `positions` (even ones)."""
+    return dips(nev, floor, 0, positions)
+
+
+def long_lived(nev: int, slot: int, floor: int = 10, dip_to: int = 6, where: Sequence[int] = ()) -> Plan:
+    """One write in pending-window slot `slot`, invoked during warm-up
+    (slot 0: event 0) and completed by the key's last event; it takes effect
+    half way.  The other ops follow dips(floor, dip_to, where), so the write
+    is among the ops pending at every cut."""
+    assert slot < floor and nev % 2 == 0 and dip_to >= 2
+    c = counts(nev, floor, [(dip_boundary(at, dip_to), dip_to) for at in where], drain=True)
+    return Plan(nev, c, hold={slot: nev - 1}, kinds={slot: "write"}, apply_at={slot: nev // 2}, distinct={slot: 1})
+
+
+def crashed_late(nev: int, slot: int, floor: int = 10, dip_to: int = 6, where: Sequence[int] = ()) -> Plan:
+    """long_lived's crashed variant: the write in `slot` gets an :info right
+    after warm-up (it keeps its slot for good), takes effect at 7/8 of the
+    key, and the op invoked next is a read that sees its value."""
+    assert slot < floor and dip_to >= 2
+    c = counts(nev, floor, [(dip_boundary(at, dip_to), dip_to) for at in where], drain=True, stuck=1)
+    return Plan(nev, c, crash={slot: floor + 2}, kinds={slot: "write"}, apply_at={slot: nev * 7 // 8},
+                distinct={slot: 1})
+
+
+def burst(nev: int, lo: int, hi: int, start: int, end: int) -> Plan:
+    """`lo` ops pending, `hi` over the boundaries start .. end: the key's
+    estimated cost (spec_targets_cost) lies in the burst."""
+    return Plan(nev, counts(nev, lo, plateaus=[(start, end, hi)], drain=True))
+
+
+def bumped(nev: int, floor: int, at: int, peak: int) -> Plan:
+    """`floor` ops pending, rising to `peak` once, at boundary `at`."""
+    return Plan(nev, counts(nev, floor, bumps=[(at, peak)], drain=True))
+
+
+def tiny(nev: int) -> Plan:
+    """0, 1 or 2 events: one failed op (its pair is dropped), one invoke that
+    never returns, one completed op."""
+    assert nev in (0, 1, 2)
+    if nev == 0:
+        return Plan(0, [0], fail_pairs=1)
+    return Plan(nev, [0, 1] if nev == 1 else [0, 1, 0])
+
+
+# ---------------------------------------------------------------- one key
+def schedule(plan: Plan, rng: random.Random) -> List[tuple]:
+    """The plan's steps: ("invoke",), ("ok", i), ("info", i), ("fail", i) --
+    i a position in the pending list (invocation order)."""
+    steps: List[tuple] = []
+    for _ in range(plan.fail_pairs):
+        steps += [("invoke",), ("fail", 0)]
+    pending: List[int] = []  # invoke ordinals
+    n_inv = 0
+    crash = dict(plan.crash)
+    for b in range(plan.nev):
+        for o, when in list(crash.items()):
+            if b >= when and o in pending:
+                steps.append(("info", pending.index(o)))
+                pending.remove(o)
+                del crash[o]
+        if plan.c[b + 1] > plan.c[b]:
+            steps.append(("invoke",))
+            pending.append(n_inv)
+            n_inv += 1
+            continue
+        due = [o for o in pending if plan.hold.get(o) == b]
+        free = [o for o in pending if o not in plan.hold and o not in crash]
+        if not due and not free:
+            raise ValueError(f"event {b}: no op left to complete")
+        # (the key's first op completes first: the stale value it writes is overwritten early)
+        o = due[0] if due else 0 if 0 in free else rng.choice(free)
+        steps.append(("ok", pending.index(o)))
+        pending.remove(o)
+    assert not crash, "a crashed op was never invoked"
+    return steps
+
+
+def history(key: int, plan: Plan, steps: Sequence[tuple], rng: random.Random, values: Sequence[int],
+            garbage: int, stale: Optional[int] = None, p_apply: float = 0.3) -> tuple:
+    """The key's op maps (no "index" yet) and the events of its directed
+    anomalies.  values: what ordinary writes and cas ops install, each used
+    at least once while writes last; garbage: read by a garbage read, written
+    by nothing; stale: written once, by the key's first op, and read by stale
+    reads."""
+    # which op each completion step takes, and each step's event
+    ev_of_ok: Dict[int, int] = {}   # event -> op
+    failing = set()
+    n_inv = ev = 0
+    sim: List[int] = []
+    for st in steps:
+        if st[0] == "invoke":
+            sim.append(n_inv)
+            n_inv += 1
+        elif st[0] == "fail":
+            failing.add(sim.pop(st[1]))
+        else:
+            sim.pop(st[1])
+    op_no = -1
+    sim = []
+    for st in steps:
+        if st[0] == "invoke":
+            op_no += 1
+            sim.append(op_no)
+            ev += op_no not in failing
+        elif st[0] == "ok":
+            ev_of_ok[ev] = sim.pop(st[1])
+            ev += 1
+        else:
+            sim.pop(st[1])
+    n_failing = len(failing)
+    # plan ordinals count the invokes that make events
+    real = [o for o in range(n_inv) if o not in failing]
+    bad_read: Dict[int, str] = {}
+    anomaly_events = []
+    for pos, kind in plan.anomalies:
+        e = min(x for x in ev_of_ok if x >= pos)
+        bad_read[ev_of_ok[e]] = kind
+        anomaly_events.append(e)
+    kinds = {real[o]: f for o, f in plan.kinds.items()}
+    apply_at = {real[o]: e for o, e in plan.apply_at.items()}
+    distinct = {real[o]: v for o, v in plan.distinct.items()}
+    plan_hold = {real[o] for o in plan.hold} | {real[o] for o in plan.crash}
+
+    rows: List[dict] = []
+    truth = None
+    free_procs: List[int] = []
+    next_proc = 0
+    live: List[dict] = []      # pending ops, invocation order
+    crashed: List[dict] = []   # :info'd ops that have not taken effect yet
+    n_writes = 0
+    stale_written = stale_done = stale_over = False
+    over_ops = []    # writes and cas ops invoked after the stale write completed
+    vals = list(values)
+
+    def new_value():
+        nonlocal n_writes
+        v = vals[n_writes % len(vals)] if n_writes < len(vals) else rng.choice(vals)
+        n_writes += 1
+        return v
+
+    def apply(op):
+        nonlocal truth
+        op["applied"] = True
+        if op["f"] == "read":
+            op["result"] = truth
+        elif op["f"] == "write":
+            truth = op["v"]
+        else:
+            assert truth is not None
+            op["v"] = [truth, new_value()]
+            op["inv"]["value"] = Tuple(key, list(op["v"]))
+            truth = op["v"][1]
+
+    ev = 0
+    op_no = -1
+    for st in steps:
+        # ops take effect at instants of their own inside their intervals
+        for op in [o for o in live + crashed if not o["applied"]]:
+            due = apply_at.get(op["no"])
+            if op["no"] in bad_read or op["no"] in failing:
+                continue
+            if due is not None:
+                if ev >= due and op not in crashed:
+                    apply(op)
+            elif op not in crashed and rng.random() < p_apply:
+                apply(op)
+        if st[0] == "invoke":
+            op_no += 1
+            if free_procs:
+                proc = free_procs.pop(rng.randrange(len(free_procs)))
+            else:
+                proc = next_proc
+                next_proc += 1
+            f = kinds.get(op_no)
+            now = False
+            # a crashed write that is due takes effect here, and this op reads its value
+            late = [o for o in crashed if ev >= apply_at.get(o["no"], 1 << 60)]
+            if op_no in bad_read:
+                f = "read"
+                if bad_read[op_no] == "stale":
+                    assert stale_over, f"key {key}: the stale value is not overwritten by a completed write yet"
+            elif op_no in failing:
+                f = "cas"   # a cas that fails: its pair is dropped
+            elif f is None and stale is not None and not stale_written:
+                f, now = "write", True
+            elif f is None and truth is None:
+                f, now = "write", True  # (a cas needs a value to succeed on)
+            elif f is None and late:
+                apply(late[0])
+                crashed.remove(late[0])
+                f, now = "read", True
+            elif f is None:
+                f = rng.choice(("read", "write", "cas"))
+            op = {"no": op_no, "f": f, "applied": False, "proc": 1000 * key + proc, "v": None, "result": None}
+            if f == "write":
+                if op_no in distinct:
+                    op["v"] = vals[distinct[op_no] % len(vals)]
+                elif stale is not None and not stale_written and op_no not in failing:
+                    op["v"], stale_written = stale, True
+                    op["is_stale"] = True
+                else:
+                    op["v"] = new_value()
+            if op_no in failing:
+                op["v"] = [vals[0], vals[-1]]
+            elif f == "cas":
+                # (redrawn where the cas takes effect; one that never returns may keep this and never succeed)
+                op["v"] = [rng.choice(vals), rng.choice(vals)]
+            op["inv"] = {"type": "invoke", "f": f, "process": op["proc"],
+                         "value": Tuple(key, None if f == "read" else op["v"])}
+            if stale_done and f != "read" and op_no not in failing and op_no not in plan_hold:
+                over_ops.append(op)
+            rows.append(op["inv"])
+            live.append(op)
+            if now:
+                apply(op)
+            ev += op_no not in failing
+            continue
+        op = live.pop(st[1])
+        if st[0] == "fail":
+            rows.append({"type": "fail", "f": op["f"], "process": op["proc"], "value": Tuple(key, op["v"])})
+            free_procs.append(op["proc"] - 1000 * key)
+            continue
+        if st[0] == "info":
+            assert op["f"] == "write", "only writes crash here"
+            rows.append({"type": "info", "f": op["f"], "process": op["proc"], "value": Tuple(key, op["v"])})
+            if not op["applied"]:
+                crashed.append(op)
+            continue
+        if op["no"] in bad_read:
+            op["result"] = garbage if bad_read[op["no"]] == "garbage" else stale
+        elif not op["applied"]:
+            apply(op)
+        if op.get("is_stale"):
+            stale_done = True
+        if any(op is o for o in over_ops):
+            stale_over = True  # a completed write has overwritten the stale value
+        rows.append({"type": "ok", "f": op["f"], "process": op["proc"],
+                     "value": Tuple(key, op["result"] if op["f"] == "read" else op["v"])})
+        free_procs.append(op["proc"] - 1000 * key)
+        ev += 1
+    assert ev == plan.nev and n_failing == plan.fail_pairs
+    return rows, anomaly_events
+
+
+# ---------------------------------------------------------------- batches
+@dataclass
+class Batch:
+    names: List[str]              # one per key, batch order
+    plans: List[Plan]
+    anomalies: List[List[int]]    # the events of each key's directed anomalies, in plan order
+    hist: H.History
+    pk: Packed
+
+    def index(self, name: str) -> int:
+        return self.names.index(name)
+
+
+def batch(cases: Sequence[tuple], seed: int, values: Sequence[int] = (0, 1, 2), garbage: int = 4,
+          stale: Optional[int] = 3, per_key_values: bool = False) -> Batch:
+    """cases: (name, plan) per key, key ids 0, 1, ... in order.  stale: every
+    key of two events or more writes it first.  per_key_values:
+    key k's values are moved by 1000 k (no two keys share a value, so the
+    packed batch numbers states per key once it has 254 values).  Asserts that
+    every key packs to the event count its plan states."""
+    rows: List[dict] = []
+    anomalies = []
+    for k, (name, plan) in enumerate(cases):
+        rng = random.Random(f"{seed}/{k}")
+        steps = schedule(plan, rng)
+        off = 1000 * k if per_key_values else 0
+        vs = values(k) if callable(values) else values
+        r, a = history(k, plan, steps, rng, [v + off for v in vs], garbage + off,
+                       None if stale is None or plan.nev < 2 else stale + off)
+        rows += r
+        anomalies.append(a)
+    for i, op in enumerate(rows):
+        op["index"] = i
+    hist = H.History.from_ops(rows)
+    pk = Packed(hist)
+    assert pk.keys == list(range(len(cases))), "keys out of order"
+    for k, (name, plan) in enumerate(cases):
+        assert len(pk.events(k)) == plan.nev, f"{name}: {len(pk.events(k))} events packed, {plan.nev} planned"
+    return Batch([n for n, _ in cases], [p for _, p in cases], anomalies, hist, pk)
+
+
+def pending_before(pk: Packed, i: int) -> np.ndarray:
+    """Ops pending at boundaries 0 .. nev of key i, from the packed words (bit 31: an :ok)."""
+    ev = pk.events(i)
+    step = np.where((ev >> 31).astype(bool), -1, 1)
+    return np.concatenate([[0], np.cumsum(step)]).astype(np.int64)
+
+
+def batch_states(pk: Packed) -> np.ndarray:
+    """States per key as the register tier counts them: 1 + the largest state
+    id of a shared table (device_api.hip:805-811), else lc_batch.key_states."""
+    from lincheck import _native as N
+    if pk.view.trans_off:
+        return N.carray(pk.view.key_states, pk.n_keys, np.uint16).astype(np.int64)
+    trans = N.carray(pk.view.trans, int(pk.view.n_trans), np.uint32)
+    mx = int(pk.view.init_state)
+    for t in trans.tolist():
+        f, a, b = t & 3, (t >> 2) & 0x7FFF, t >> 17
+        if f in (1, 3) and a != 0x7FFF:
+            mx = max(mx, a)
+        if f in (2, 3):
+            mx = max(mx, b)
+    return np.full(pk.n_keys, mx + 1, np.int64)
+
+
+# ---------------------------------------------------------------- the batches
+# (tests/test_edgegen.py asserts what each is built for; tests/test_gpu_register_edges.py runs them)
+RAGGED_LENGTHS = [0, 1, 2] + [L + d for L in (64, 128, 256, 384, 512, 768, 1024, 3072, 4096) for d in (-1, 0, 1)]
+NEV = 1024                                # (c), (d), (e): eff = 8 at 8 segments, targets at multiples of 128
+TARGETS = spec_targets(NEV, 8)
+SEG5 = 5 * 128 + 70                       # inside segment 5 wherever the cuts fall in their windows
+DIP_TARGET = 5 * 128                      # the target whose window the single dips lie in
+
+
+def ragged_cases() -> List[tuple]:
+    """(a): every length, each with a valid key, one whose first and one whose
+    last :ok fails; empty and one-event keys first, in the middle and last."""
+    cases = [("empty-first", tiny(0)), ("one-first", tiny(1))]
+    for n, nev in enumerate(RAGGED_LENGTHS):
+        if n == len(RAGGED_LENGTHS) // 2:
+            cases += [("empty-mid", tiny(0)), ("one-mid", tiny(1))]
+        plan = tiny(nev) if nev <= 2 else Plan(nev, counts(nev, 3 + n % 4, drain=True))
+        cases.append((f"len{nev}-valid", plan))
+        if nev >= 2:  # (shorter keys have no :ok)
+            cases.append((f"len{nev}-first_ok", plan.with_anomalies((0, "garbage"))))
+            cases.append((f"len{nev}-last_ok", plan.with_anomalies((plan.ok_events()[-1], "garbage"))))
+    return cases + [("empty-last", tiny(0)), ("one-last", tiny(1))]
+
+
+def compact_cases(n_keys: int = 2600) -> List[tuple]:
+    """(b): (a)'s keys, then filler keys of 2-6 events (every seventh with a
+    garbage read) up to n_keys."""
+    cases = ragged_cases()
+    n = 0
+    while len(cases) < n_keys:
+        nev = 2 + n % 5
+        plan = Plan(nev, counts(nev, 2 + n % 2, drain=True))
+        cases.append((f"filler{n}", plan.with_anomalies((0, "garbage")) if n % 7 == 3 else plan))
+        n += 1
+    return cases
+
+
+def both(name: str, plan: Plan) -> List[tuple]:
+    """The profile valid, and with a garbage read in segment 5."""
+    return [(f"{name}-valid", plan), (f"{name}-garbage_seg5", plan.with_anomalies((SEG5, "garbage")))]
+
+
+def profile_cases() -> List[tuple]:
+    cases = both("rolling7", rolling(NEV, 7, first="invoke"))     # counts 7, 8: complete-first would touch 6
+    cases += both("rolling7_touching6", rolling(NEV, 7))          # counts 6, 7: a cut at every target, 6 pending
+    for P in (8, 9, 10):
+        cases += both(f"rolling{P}", rolling(NEV, P))
+    for d in (0, 3, 6, 7):
+        for off in (0, 32, 64, 65):
+            cases += both(f"dip{d}_at+{off}", dips(NEV, 10, d, [DIP_TARGET + off]))
+    cases += both("dip6_every_target", dips(NEV, 10, 6, TARGETS, wide=True))  # :oks at 9 and at 10 pending
+    cases += both("burst_same_boundary", burst(NEV, 5, 10, 400, 520))
+    cases += both("long_lived_slot0", long_lived(NEV, 0, where=TARGETS))
+    cases += both("long_lived_slot9", long_lived(NEV, 9, where=TARGETS))
+    cases += both("crashed_write_read_late", crashed_late(NEV, 3, where=TARGETS))
+    return cases
+
+
+ANOMALY_CUT = 512
+ANOMALY_FLOOR = 6
+
+
+def anomaly_cases() -> List[tuple]:
+    """(d): nothing pending at every multiple of 128; failing :oks placed
+    against the cuts and the default checkpoints."""
+    q = quiescent_at(NEV, TARGETS, floor=ANOMALY_FLOOR)
+    ck1, ck2 = SPEC_CK_DEFAULT
+    cases = [("valid#0", q), ("valid#1", q), ("valid#2", q)]
+    for s, cut in enumerate(TARGETS, 1):
+        cases.append((f"first_ok_after_cut{s}-stale", q.with_anomalies((cut, "stale"))))
+    for kind in ("garbage", "stale"):
+        cases.append((f"last_ok_before_cut-{kind}", q.with_anomalies((ANOMALY_CUT - 1, kind))))
+        cases.append((f"at_ck1-{kind}", q.with_anomalies((ANOMALY_CUT + ck1, kind))))
+        cases.append((f"at_ck2-{kind}", q.with_anomalies((ANOMALY_CUT + ck2, kind))))
+        cases.append((f"last_event-{kind}", q.with_anomalies((NEV - 1, kind))))
+    cases.append(("segment0_only-garbage", q.with_anomalies((60, "garbage"))))
+    cases.append(("segment0_only-stale", q.with_anomalies((100, "stale"))))
+    cases.append(("two-garbage_seg2-stale_seg5", q.with_anomalies((2 * 128 + 40, "garbage"), (5 * 128 + 40, "stale"))))
+    cases.append(("two-stale_seg2-garbage_seg5", q.with_anomalies((2 * 128 + 40, "stale"), (5 * 128 + 40, "garbage"))))
+    cases.append(("every_segment", q.with_anomalies(*[(128 * s + 50, "stale" if s % 2 else "garbage")
+                                                      for s in range(8)])))
+    return cases
+
+
+def limit_cases(n: int = 12, bump_key: Optional[int] = None) -> List[tuple]:
+    """(e): dips(8, 4, every target) keys, every third with a stale read;
+    bump_key: that key reaches 11 pending once."""
+    cases = []
+    for k in range(n):
+        plan = dips(NEV, 8, 4, TARGETS)
+        if bump_key is not None:
+            plan = dips(NEV, 10, 6, TARGETS)
+            if k == bump_key:
+                plan = Plan(NEV, counts(NEV, 10, [(t, 6) for t in TARGETS], bumps=[(451, 11)], drain=True))
+        name = "reaches11" if k == bump_key and bump_key is not None else f"key{k}"
+        if k % 3 == 1:
+            cases.append((f"{name}-stale_at{100 + 77 * k}", plan.with_anomalies((100 + 77 * k, "stale"))))
+        else:
+            cases.append((f"{name}-valid", plan))
+    return cases
+
+
+BATCHES = {
+    # name: (cases, batch() keywords)
+    "ragged": (ragged_cases, dict(seed=11)),
+    "compact": (compact_cases, dict(seed=11)),
+    "profiles": (profile_cases, dict(seed=12)),
+    "anomalies": (anomaly_cases, dict(seed=13)),
+    "states32": (limit_cases, dict(seed=14, values=range(30), stale=30, garbage=99)),
+    "states33": (limit_cases, dict(seed=15, values=range(31), stale=31, garbage=99)),
+    "states32_33_mixed": (limit_cases, dict(seed=16, per_key_values=True, stale=31, garbage=99,
+                                            values=lambda k: range(30 + k % 2))),
+    "width11": (lambda: limit_cases(bump_key=5), dict(seed=17)),
+    "values5": (anomaly_cases, dict(seed=18, values=range(4), stale=4, garbage=99)),
+    "values6": (anomaly_cases, dict(seed=19, values=range(5), stale=5, garbage=99)),
+}
+_built: Dict[str, Batch] = {}
+
+
+def get(name: str) -> Batch:
+    """The named batch, built once per process."""
+    if name not in _built:
+        cases, kw = BATCHES[name]
+        _built[name] = batch(cases(), **kw)
+    return _built[name]
