@@ -398,7 +398,11 @@ typedef struct lc_opts {
 #define LC_PATH_SET_DIRECT   0x8000 /* lc_set_check, HBM tier: k_set_mark's bits leave by
                                        atomics from the lanes, never through a
                                        workgroup's LDS tile (A/B runs and tests)      */
-#define LC_PATH_ALL          0xFFFF
+#define LC_PATH_NODE_SERIAL  0x10000 /* lc_check_node_async: every step's search on one
+                                        stream, in turn (else consecutive register-tier
+                                        steps search on two streams and overlap; A/B runs
+                                        and tests -- the records are the same either way) */
+#define LC_PATH_ALL          0x1FFFF
 
 /* lc_opts.flags */
 #define LC_OPT_COUNT_PROBES 0x1  /* count successor-config probes (lc_stats.probes,
@@ -509,14 +513,16 @@ void lc_dev_batch_free(lc_dev_batch *db);
 #define LC_DEV_ASYNC  2
 int  lc_check_device(lc_ctx *ctx, const lc_dev_batch *db, lc_result *r,
                      int flags, lc_stats *s);
-/* Wait for every step enqueued on the context.  Returns the number of
- * LC_DEV_ASYNC steps since the previous lc_wait (or a negative LC_E_* code);
- * s->kernel_ms = their span (HIP events, first start .. last end) and
- * s->tier0_ms = span / count. */
+/* Wait for every step enqueued on the context, on both of its search
+ * streams.  Returns the number of LC_DEV_ASYNC steps since the previous
+ * lc_wait (or a negative LC_E_* code); s->kernel_ms = their span (HIP events,
+ * first start .. last end on either stream) and s->tier0_ms = span / count
+ * (overlapping steps: less than one step's search). */
 int  lc_wait(lc_ctx *ctx, lc_stats *s);
 /* Wait until the LC_DEV_ASYNC step `back` steps before the latest (0 = the
- * latest, at most 3) has finished, leaving later ones running; with no such
- * step on record, wait for everything on the context's stream.  Returns
+ * latest, at most 3) has finished, leaving later ones running; steps count in
+ * the order they were enqueued, whichever stream searched them.  With no such
+ * step on record, wait for everything enqueued on the context.  Returns
  * LC_E_INVALID, naming the key, when a finished step's batch was malformed
  * (an error a later, still running step has raised already may be reported
  * here too); the error is cleared then. */
@@ -542,13 +548,19 @@ int  lc_comm_id(uint8_t *out);
 int  lc_check_node(lc_ctx *ctx, const lc_batch *shard, int64_t block, uint64_t *node, lc_stats *s);
 /* Pipelined lc_check_node.  A step that is the register tier alone
  * (every key fits it, no probe counting, node page-locked: lc_host_alloc)
- * is only enqueued and returns 1:
- * its upload overlaps the search of the step before it (two steps in flight)
- * and its records are in `node` once lc_wait (or lc_wait_step over it)
- * returns; errors surface there.  The shard's arrays and `node` must stay
- * untouched until then.  One rank (no communicator): the search writes the
- * records straight into `node` (device-mapped), and lc_node_records has none
- * of them.  Any other step runs as lc_check_node (returns 0). */
+ * is only enqueued and returns 1: up to three steps are in flight, one
+ * uploading and -- without a communicator -- two searching at once on two
+ * streams (a step's workgroups take the slots the previous step's finished
+ * blocks free; LC_PATH_NODE_SERIAL keeps one search at a time, as a
+ * communicator does).  Its records are in `node` once lc_wait (or
+ * lc_wait_step over it) returns; errors surface there.  The shard's arrays
+ * and `node` must stay untouched until then.  A buffer given to several
+ * steps in flight holds, after that wait, the records of the latest step
+ * enqueued with it: such a step's records leave through device memory, behind
+ * the end of the earlier step.  One rank (no communicator): otherwise the
+ * search writes the records straight into `node` (device-mapped); either way
+ * lc_node_records has none of them.  Any other step runs as lc_check_node
+ * (returns 0). */
 int  lc_check_node_async(lc_ctx *ctx, const lc_batch *shard, int64_t block, uint64_t *node, lc_stats *s);
 /* Page-locked host memory (for lc_check_node_async's records). */
 void *lc_host_alloc(size_t bytes);

@@ -33,6 +33,7 @@
 #include "device_perf.hpp"
 #include "device_set.hpp"
 #include "step_plan.hpp"
+#include "lane_plan.hpp"
 
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
@@ -235,13 +236,68 @@ constexpr int ERR_RING = 24, ERR_TAKEN = 32;
 // Most device memory the speculative segments' per-key workspaces may take.
 constexpr uint64_t SPEC_WS_MAX_BYTES = 8ull << 30;
 
-// One device of a context: its stream, scratch and result arrays.
+// What a search step reaches through stream order, one copy per search
+// lane: consecutive enqueued register-tier steps of lc_check_node_async
+// search on the two lanes in turn and overlap (lane_plan.hpp); every other
+// step runs on lane 0, after joining lane 1.
+struct Lane {
+    hipStream_t stream = nullptr;
+    // a step's verdicts when its results stay in the context (RES_CTX, RES_HOST)
+    int8_t *valid = nullptr;
+    int32_t *fail_event = nullptr;
+    uint8_t *cause = nullptr;
+    // speculative segments: each wave's 9-10-pending workspace, the rerun list
+    uint32_t *spec_ws = nullptr;
+    size_t spec_ws_words = 0;
+    uint32_t *spec_fin = nullptr;  // exact speculative segments: each run's saved set
+    size_t spec_fin_words = 0;
+    int32_t *spec_rr = nullptr;    // two rerun counts (used in turn), then the rerun list
+    int64_t spec_rr_cap = 0;
+    int spec_parity = 0;
+    // Device copies of T0's Args (read once per key): a ring of 12, so steps
+    // alternating between result sets (the N > 1 bench), or pipelined steps
+    // between their staging batches and error words (3 x 4 in turn on one
+    // lane, 3 x 2 on each of two), each find theirs without a copy; a slot's
+    // pinned staging copy is rewritten only after the copy out of it
+    // (args_ev) has run.
+    static constexpr int ARGS_RING = 12;
+    lcd::Args *dargs = nullptr;    // [ARGS_RING]
+    lcd::Args *hargs = nullptr;    // [ARGS_RING] pinned
+    hipEvent_t args_ev[ARGS_RING] = {};
+    bool args_ok[ARGS_RING] = {};
+    uint32_t args_next = 0;
+    // an overlapping step's records when they cannot go straight into the
+    // caller's buffer (a step still in flight was given it too)
+    uint64_t *rec = nullptr;
+    int64_t rec_cap = 0;
+    hipEvent_t done = nullptr;  // lane 1: everything enqueued on it, for lane 0 to join
+    void free_all() {
+        dfree(valid); dfree(fail_event); dfree(cause);
+        dfree(spec_ws); dfree(spec_rr); dfree(spec_fin); dfree(dargs); dfree(rec);
+        if (hargs) (void)hipHostFree(hargs);
+        hargs = nullptr;
+        for (hipEvent_t &e : args_ev) {
+            if (e) (void)hipEventDestroy(e);
+            e = nullptr;
+        }
+        if (done) (void)hipEventDestroy(done);
+        done = nullptr;
+    }
+};
+
+// One device of a context: its streams, scratch and result arrays.
 struct Dev {
     const lc_opts *o = nullptr;  // the context's options
     int device = 0;
     int cu_count = 256;
-    hipStream_t stream = nullptr;
-    hipStream_t vstream = nullptr;  // validation of host-unchecked batches, beside T0
+    hipStream_t stream = nullptr;   // lane 0's (lane[0].stream): every step but the overlapping ones' second
+    hipStream_t stream1 = nullptr;  // lane 1's: every second overlapping search; else the validation of
+                                    // host-unchecked batches, beside T0
+    Lane lane[lc::LANES];
+    bool lane1_live = false;        // lane 1 has work lane 0 has not joined
+    bool lane1_wait_start = false;  // lane 1's next search first waits for run_start
+    uint64_t run_n = 0;             // overlapping steps since the lanes were last joined
+    hipEvent_t run_start = nullptr; // lane 0, ahead of such a run's first search (its set-up done)
     hipStream_t cstream = nullptr;  // lc_check_node's chunked uploads, ahead of the searches
     hipStream_t estream = nullptr;  // lc_wait_step's error reads (behind no upload or step)
     static constexpr int NODE_CHUNKS = 4;
@@ -265,22 +321,9 @@ struct Dev {
     unsigned long long *acc = nullptr;
     int32_t *counters = nullptr;
     unsigned long long *hctl = nullptr;  // pinned host copy of ctl
-    int8_t *valid = nullptr;
-    int32_t *fail_event = nullptr;
-    uint8_t *cause = nullptr;
     uint32_t *peak = nullptr;
     uint64_t *final_cfg = nullptr;
     uint32_t *n_final = nullptr;
-    // Device copies of T0's Args (read once per key): a ring of 4, so steps
-    // alternating between result sets (the N > 1 bench) each find theirs
-    // without a copy; a slot's pinned staging copy is rewritten only after
-    // the copy out of it (args_ev) has run.
-    static constexpr int ARGS_RING = 4;
-    lcd::Args *dargs = nullptr;    // [ARGS_RING]
-    lcd::Args *hargs = nullptr;    // [ARGS_RING] pinned
-    hipEvent_t args_ev[ARGS_RING] = {};
-    bool args_ok[ARGS_RING] = {};
-    uint32_t args_next = 0;
     DevBatch *staged = nullptr;    // lc_check_batch's staging batch (device arrays reused)
     // T0-only steps skip re-zeroing the control block: the ticket continues
     // from where the previous such step left it.
@@ -292,29 +335,23 @@ struct Dev {
     uint32_t *seg_cnt = nullptr, *seg_end = nullptr, *seg_out = nullptr, *seg_work = nullptr;
     uint32_t *seg_rerun = nullptr, *seg_rerun_init = nullptr;
     int32_t *seg0_fev = nullptr, *seg_ctl = nullptr;
-    // speculative segments: each wave's 9-10-pending workspace, the rerun list
-    uint32_t *spec_ws = nullptr;
-    size_t spec_ws_words = 0;
-    uint32_t *spec_fin = nullptr;  // exact speculative segments: each run's saved set
-    size_t spec_fin_words = 0;
-    int32_t *spec_rr = nullptr;    // two rerun counts (used in turn), then the rerun list
-    int64_t spec_rr_cap = 0;
-    int spec_parity = 0;
     // node records (lc_check_node): this rank's block and the gathered node
     uint64_t *send = nullptr, *node = nullptr;
     int64_t node_cap = 0, node_n = 0;
     uint64_t *rec_out = nullptr;  // set around a node step's search: finish_key writes the records there
     uint64_t *hnode = nullptr;  // pinned landing area of the node's records (lc_check_node)
     int64_t hnode_cap = 0;
-    // lc_check_node_async: two staging batches used in turn, so a step's
-    // upload (on cstream) runs while the step before it searches; pipe_ready
+    // lc_check_node_async: three staging batches used in turn, so a step's
+    // upload (on cstream) runs while the two steps before it search; pipe_ready
     // = a slot's upload is done; the step that read a slot is done when its
-    // ring event (async_seq pipe_seq[s]) is
-    static constexpr int PIPE = 2;
+    // ring event (async_seq pipe_seq[s]) is; pipe_lo .. pipe_hi = the
+    // caller's record buffer that step was given
+    static constexpr int PIPE = lc::LANE_SLOTS;
     DevBatch *pipe[PIPE] = {};
     hipEvent_t pipe_ready[PIPE] = {};
     uint64_t pipe_seq[PIPE] = {};
     bool pipe_busy[PIPE] = {};
+    uint64_t pipe_lo[PIPE] = {}, pipe_hi[PIPE] = {};
     uint64_t pipe_next = 0;
     // T3 (HBM tier) workspaces: narrow / wide configs
     struct Ws {
@@ -346,19 +383,18 @@ struct Dev {
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
+        if (stream1) (void)hipStreamSynchronize(stream1);
         lcs::set_dev_free(setdev);
         lcp::perf_dev_free(perfdev);
-        dfree(lists); dfree(ctl); dfree(valid); dfree(fail_event);
+        dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
-        dfree(cause); dfree(peak); dfree(final_cfg); dfree(n_final);
-        dfree(ws[0].base); dfree(ws[1].base); dfree(lws.base); dfree(dargs); dfree(send); dfree(node);
+        dfree(peak); dfree(final_cfg); dfree(n_final);
+        dfree(ws[0].base); dfree(ws[1].base); dfree(lws.base); dfree(send); dfree(node);
         dfree(wws[0].base); dfree(wws[1].base); dfree(analyzer);
         dfree(seg_cnt); dfree(seg_end); dfree(seg_out); dfree(seg_work); dfree(seg_rerun); dfree(seg_rerun_init);
-        dfree(seg0_fev); dfree(seg_ctl); dfree(spec_ws); dfree(spec_rr); dfree(spec_fin);
-        if (hargs) (void)hipHostFree(hargs);
+        dfree(seg0_fev); dfree(seg_ctl);
+        for (Lane &l : lane) l.free_all();
         if (hnode) (void)hipHostFree(hnode);
-        for (hipEvent_t &e : args_ev)
-            if (e) (void)hipEventDestroy(e);
         delete staged;
         for (int i = 0; i < PIPE; ++i) {
             delete pipe[i];
@@ -373,10 +409,9 @@ struct Dev {
         if (cstream) (void)hipStreamDestroy(cstream);
         if (estream) (void)hipStreamSynchronize(estream);
         if (estream) (void)hipStreamDestroy(estream);
-        if (vstream) (void)hipStreamSynchronize(vstream);
-        for (hipEvent_t e : {e0, e1, et0, et3a, et3b, ea0, ea1, vin, vdone})
+        for (hipEvent_t e : {e0, e1, et0, et3a, et3b, ea0, ea1, vin, vdone, run_start})
             if (e) (void)hipEventDestroy(e);
-        if (vstream) (void)hipStreamDestroy(vstream);
+        if (stream1) (void)hipStreamDestroy(stream1);
         for (hipEvent_t &e : ring)
             if (e) (void)hipEventDestroy(e);
         if (stream) (void)hipStreamDestroy(stream);
@@ -408,21 +443,47 @@ struct lc_ctx {
     }
 };
 
+// Lane 0 behind everything enqueued on lane 1: whatever follows on lane 0
+// (any step but an overlapping one, a wait) sees all that was enqueued
+// before it.  The next run of overlapping steps starts on lane 0 again.
+static int join_lanes(Dev *c) {
+    if (c->lane1_live) {
+        HIPCHK(hipEventRecord(c->lane[1].done, c->stream1));
+        HIPCHK(hipStreamWaitEvent(c->stream, c->lane[1].done, 0));
+        c->lane1_live = false;
+    }
+    c->run_n = 0;
+    return LC_OK;
+}
+
+// The host behind both lanes (before a buffer their steps use is freed).
+static int drain_lanes(Dev *c) {
+    HIPCHK(hipStreamSynchronize(c->stream1));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    c->lane1_live = c->lane1_wait_start = false;
+    c->run_n = 0;
+    return LC_OK;
+}
+
 static int ensure_capacity(Dev *c, int64_t n_keys) {
     if (n_keys <= c->cap_keys) return LC_OK;
     int64_t cap = std::max<int64_t>(n_keys, 1024);
-    dfree(c->lists); dfree(c->valid); dfree(c->fail_event); dfree(c->cause);
+    if (c->n_async) LCCHK(drain_lanes(c));  // an enqueued step may still write what goes
+    dfree(c->lists);
     dfree(c->peak); dfree(c->final_cfg); dfree(c->n_final); dfree(c->analyzer);
     HIPCHK(dalloc(&c->lists, (size_t)cap * 5));
     HIPCHK(dalloc(&c->analyzer, (size_t)cap));
-    HIPCHK(dalloc(&c->valid, (size_t)cap));
-    HIPCHK(dalloc(&c->fail_event, (size_t)cap));
-    HIPCHK(dalloc(&c->cause, (size_t)cap));
+    for (Lane &l : c->lane) {
+        dfree(l.valid); dfree(l.fail_event); dfree(l.cause);
+        HIPCHK(dalloc(&l.valid, (size_t)cap));
+        HIPCHK(dalloc(&l.fail_event, (size_t)cap));
+        HIPCHK(dalloc(&l.cause, (size_t)cap));
+        for (bool &v : l.args_ok) v = false;
+    }
     HIPCHK(dalloc(&c->peak, (size_t)cap));
     HIPCHK(dalloc(&c->final_cfg, (size_t)cap * (size_t)c->o->max_final * 2));
     HIPCHK(dalloc(&c->n_final, (size_t)cap));
     c->cap_keys = cap;
-    for (bool &v : c->args_ok) v = false;
     return LC_OK;
 }
 
@@ -520,7 +581,12 @@ static int dev_init(Dev *c, int device) {
     c->cu_count = prop.multiProcessorCount;
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    HIPCHK(hipStreamCreateWithFlags(&c->vstream, hipStreamNonBlocking));
+    // (four streams, lane 1 doubling as the validation stream: a process
+    // has four hardware queues by default, and a fifth stream would share
+    // one with another and run behind it)
+    HIPCHK(hipStreamCreateWithFlags(&c->stream1, hipStreamNonBlocking));
+    c->lane[0].stream = c->stream;
+    c->lane[1].stream = c->stream1;
     HIPCHK(hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking));
     HIPCHK(hipStreamCreateWithFlags(&c->estream, hipStreamNonBlocking));
     HIPCHK(hipEventCreateWithFlags(&c->vin, hipEventDisableTiming));
@@ -533,9 +599,13 @@ static int dev_init(Dev *c, int device) {
     HIPCHK(hipMemset(c->ctl, 0, 32 * sizeof(unsigned long long)));
     HIPCHK(hipHostMalloc((void **)&c->hctl, 32 * sizeof(unsigned long long), hipHostMallocDefault));
     std::memset(c->hctl, 0, 32 * sizeof(unsigned long long));
-    HIPCHK(dalloc(&c->dargs, Dev::ARGS_RING));
-    HIPCHK(hipHostMalloc((void **)&c->hargs, sizeof(lcd::Args) * Dev::ARGS_RING, hipHostMallocDefault));
-    for (hipEvent_t &e : c->args_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->run_start, hipEventDisableTiming));
+    for (Lane &l : c->lane) {
+        HIPCHK(dalloc(&l.dargs, Lane::ARGS_RING));
+        HIPCHK(hipHostMalloc((void **)&l.hargs, sizeof(lcd::Args) * Lane::ARGS_RING, hipHostMallocDefault));
+        for (hipEvent_t &e : l.args_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
+    }
     return LC_OK;
 }
 
@@ -1212,6 +1282,20 @@ struct Step {
     int32_t n_deep = 0, n_widek = 0;
     float ms = 0, ms0 = 0, ms3 = 0, msw = 0;
     uint64_t wgl_keys = 0, wgl_steps = 0, wgl_spilled = 0;
+    Lane *L = nullptr;             // the lane whose scratch and result arrays the step uses
+    hipStream_t q = nullptr;       // ... and its stream (lane 0's for every step but an overlapping one)
+    const struct LaneUse *lu = nullptr;
+};
+
+// How lc_check_node_async places an enqueued step (lane_plan.hpp): its lane,
+// and for records that go through the lane's block (Lane::rec) their download
+// -- n records to dst behind the searches' launches, once `after` has passed.
+struct LaneUse {
+    int lane = 0;
+    bool overlap = false;
+    uint64_t *dst = nullptr;
+    size_t n = 0;
+    hipEvent_t after = nullptr;
 };
 
 // The work lists between the tiers (Dev::lists) and their counts (Dev::counters).
@@ -1244,7 +1328,7 @@ static void step_args(Step &s, int64_t key0, int64_t res_off) {
         a.valid = r->valid; a.fail_event = r->fail_event; a.cause = r->cause;
         a.peak = r->peak_configs; a.final_cfg = r->final_configs; a.n_final = r->n_final;
     } else {
-        a.valid = c->valid + res_off; a.fail_event = c->fail_event + res_off; a.cause = c->cause + res_off;
+        a.valid = s.L->valid + res_off; a.fail_event = s.L->fail_event + res_off; a.cause = s.L->cause + res_off;
         a.peak = (mode == RES_HOST && r->peak_configs) ? c->peak : nullptr;
         a.final_cfg = (mode == RES_HOST && r->final_configs) ? c->final_cfg : nullptr;
         a.n_final = (mode == RES_HOST && r->n_final) ? c->n_final : nullptr;
@@ -1277,11 +1361,11 @@ static lc::StepIn step_in(const Step &s, bool allow_async) {
 
 // The 32-bit event words every kernel but k_spec reads, widened once per
 // upload from a batch's 16-bit ones.
-static int ensure_ev32(Dev *c, const DevBatch *d) {
+static int ensure_ev32(Dev *c, const DevBatch *d, hipStream_t q) {
     if (d->ev32_ready || !d->n_events) return LC_OK;
     const uint64_t n4 = (d->n_events + 3) / 4;
     const int blocks = (int)std::min<uint64_t>((n4 + 255) / 256, (uint64_t)c->cu_count * 8);
-    hipLaunchKernelGGL(k_widen16, dim3(std::max(blocks, 1)), dim3(256), 0, c->stream, d->events16, d->events,
+    hipLaunchKernelGGL(k_widen16, dim3(std::max(blocks, 1)), dim3(256), 0, q, d->events16, d->events,
                        d->n_events);
     HIPCHK(hipGetLastError());
     d->ev32_ready = true;
@@ -1290,9 +1374,9 @@ static int ensure_ev32(Dev *c, const DevBatch *d) {
 
 // Zero the control block: everything but the error words (a malformed batch
 // reported at the next wait keeps them until then).
-static int zero_control(Dev *c) {
-    HIPCHK(hipMemsetAsync(c->ctl, 0, 4 * sizeof(unsigned long long) + 4 * sizeof(int32_t), c->stream));
-    HIPCHK(hipMemsetAsync(c->counters + 6, 0, 10 * sizeof(int32_t), c->stream));
+static int zero_control(Dev *c, hipStream_t q) {
+    HIPCHK(hipMemsetAsync(c->ctl, 0, 4 * sizeof(unsigned long long) + 4 * sizeof(int32_t), q));
+    HIPCHK(hipMemsetAsync(c->counters + 6, 0, 10 * sizeof(int32_t), q));
     return LC_OK;
 }
 
@@ -1305,9 +1389,9 @@ static int readback(const Step &s) {
     HIPCHK(hipEventRecord(c->e1, c->stream));
     HIPCHK(hipMemcpyAsync(c->hctl, c->ctl, CTL_BYTES, hipMemcpyDeviceToHost, c->stream));
     if (s.mode == RES_HOST && K > 0) {
-        HIPCHK(hipMemcpyAsync(r->valid, c->valid, K, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(r->fail_event, c->fail_event, K * 4, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(r->cause, c->cause, K, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(r->valid, s.L->valid, K, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(r->fail_event, s.L->fail_event, K * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(r->cause, s.L->cause, K, hipMemcpyDeviceToHost, c->stream));
         if (r->peak_configs) HIPCHK(hipMemcpyAsync(r->peak_configs, c->peak, K * 4, hipMemcpyDeviceToHost, c->stream));
         if (r->final_configs)
             HIPCHK(hipMemcpyAsync(r->final_configs, c->final_cfg, K * c->o->max_final * 16, hipMemcpyDeviceToHost,
@@ -1324,9 +1408,9 @@ static int search_wgl(Step &s, lc_stats *st) {
     Dev *c = s.c;
     const DevBatch *d = s.d;
     const int64_t K = s.K;
-    LCCHK(zero_control(c));
+    LCCHK(zero_control(c, c->stream));
     c->ticket_live = false;
-    LCCHK(ensure_ev32(c, d));
+    LCCHK(ensure_ev32(c, d, c->stream));
     if (s.a.n_final && K > 0) HIPCHK(hipMemsetAsync(s.a.n_final, 0, (size_t)K * 4, c->stream));
     HIPCHK(hipEventRecord(c->e0, c->stream));
     if (!d->validated && K > 0) {  // the per-event checks the host skipped, ahead of the walk
@@ -1360,7 +1444,7 @@ static int search_wgl(Step &s, lc_stats *st) {
 template <class T, class N>
 static int grow_dev(Dev *c, T *&ptr, N &have, N need) {
     if (need <= have) return LC_OK;
-    if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));
+    if (c->n_async) LCCHK(drain_lanes(c));
     dfree(ptr);
     have = 0;
     HIPCHK(dalloc(&ptr, (size_t)need));
@@ -1368,14 +1452,16 @@ static int grow_dev(Dev *c, T *&ptr, N &have, N need) {
     return LC_OK;
 }
 
-// k_spec's per-key workspaces, the exact runs' saved sets, the rerun list.
+// k_spec's per-key workspaces, the exact runs' saved sets, the rerun list:
+// the step's lane's own.
 static int ensure_spec_ws(const Step &s) {
     Dev *c = s.c;
-    LCCHK(grow_dev(c, c->spec_ws, c->spec_ws_words, lcd::spec_ws_words(s.K, s.p.segs)));
-    LCCHK(grow_dev(c, c->spec_fin, c->spec_fin_words, s.p.exact ? lcd::spec_fin_words(s.K, s.p.segs) : (size_t)0));
-    const int64_t rr_had = c->spec_rr_cap;
-    LCCHK(grow_dev(c, c->spec_rr, c->spec_rr_cap, s.K + 2));
-    if (c->spec_rr_cap != rr_had) HIPCHK(hipMemsetAsync(c->spec_rr, 0, 2 * sizeof(int32_t), c->stream));
+    Lane &L = *s.L;
+    LCCHK(grow_dev(c, L.spec_ws, L.spec_ws_words, lcd::spec_ws_words(s.K, s.p.segs)));
+    LCCHK(grow_dev(c, L.spec_fin, L.spec_fin_words, s.p.exact ? lcd::spec_fin_words(s.K, s.p.segs) : (size_t)0));
+    const int64_t rr_had = L.spec_rr_cap;
+    LCCHK(grow_dev(c, L.spec_rr, L.spec_rr_cap, s.K + 2));
+    if (L.spec_rr_cap != rr_had) HIPCHK(hipMemsetAsync(L.spec_rr, 0, 2 * sizeof(int32_t), s.q));
     return LC_OK;
 }
 
@@ -1387,10 +1473,12 @@ static int t0_args(Step &s, lcd::Args *a0) {
     if (s.p.t0_step && c->ticket_live && !s.p.competition) {
         s.ticket_base = c->ticket_next;
     } else {
-        LCCHK(zero_control(c));
+        // (of a run of overlapping steps only the first comes here, on lane
+        // 0, ahead of run_start: the later ones find the ticket live)
+        LCCHK(zero_control(c, s.q));
     }
     c->ticket_live = false;
-    if (s.a.n_final && s.K > 0) HIPCHK(hipMemsetAsync(s.a.n_final, 0, (size_t)s.K * 4, c->stream));
+    if (s.a.n_final && s.K > 0) HIPCHK(hipMemsetAsync(s.a.n_final, 0, (size_t)s.K * 4, s.q));
     const Lists l = lists_of(c);
     *a0 = s.a;
     a0->order = s.d->order; a0->n_order = (int32_t)s.K; a0->n_in = nullptr; a0->ticket = c->counters + 8;
@@ -1403,20 +1491,21 @@ static int t0_args(Step &s, lcd::Args *a0) {
 // T0 reads the result/counter/list pointers from a device copy of its
 // Args: a ring slot holding these Args, else the next slot, refreshed
 // (device copies are rewritten in stream order, after the launches that
-// read them)
-static int args_slot(Dev *c, const lcd::Args &a0, lcd::Args **dargs) {
+// read them: the ring is the lane's own, whose stream every step of the lane
+// runs on)
+static int args_slot(Lane &L, const lcd::Args &a0, lcd::Args **dargs) {
     int aslot = -1;
-    for (int q = 0; q < Dev::ARGS_RING && aslot < 0; ++q)
-        if (c->args_ok[q] && std::memcmp(c->hargs + q, &a0, sizeof a0) == 0) aslot = q;
+    for (int q = 0; q < Lane::ARGS_RING && aslot < 0; ++q)
+        if (L.args_ok[q] && std::memcmp(L.hargs + q, &a0, sizeof a0) == 0) aslot = q;
     if (aslot < 0) {
-        aslot = (int)(c->args_next++ % Dev::ARGS_RING);
-        HIPCHK(hipEventSynchronize(c->args_ev[aslot]));  // its staging copy has been read
-        std::memcpy(c->hargs + aslot, &a0, sizeof a0);
-        HIPCHK(hipMemcpyAsync(c->dargs + aslot, c->hargs + aslot, sizeof(lcd::Args), hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipEventRecord(c->args_ev[aslot], c->stream));
-        c->args_ok[aslot] = true;
+        aslot = (int)(L.args_next++ % Lane::ARGS_RING);
+        HIPCHK(hipEventSynchronize(L.args_ev[aslot]));  // its staging copy has been read
+        std::memcpy(L.hargs + aslot, &a0, sizeof a0);
+        HIPCHK(hipMemcpyAsync(L.dargs + aslot, L.hargs + aslot, sizeof(lcd::Args), hipMemcpyHostToDevice, L.stream));
+        HIPCHK(hipEventRecord(L.args_ev[aslot], L.stream));
+        L.args_ok[aslot] = true;
     }
-    *dargs = c->dargs + aslot;
+    *dargs = L.dargs + aslot;
     return LC_OK;
 }
 
@@ -1445,7 +1534,7 @@ static lcd::SpecLaunch spec_launch(const Step &s) {
     const lc_opts &o = *c->o;
     lcd::SpecLaunch l{};
     l.segs = s.p.segs;
-    l.ws = c->spec_ws; l.rr = c->spec_rr; l.parity = c->spec_parity;
+    l.ws = s.L->spec_ws; l.rr = s.L->spec_rr; l.parity = s.L->spec_parity;
     // (spec_ck == 0: the defaults; else (ck1 + 1) | (ck2 + 1) << 16)
     l.ck1 = o.spec_ck ? ((uint32_t)o.spec_ck & 0xFFFFu) - 1u : 32u;
     l.ck2 = o.spec_ck ? ((uint32_t)o.spec_ck >> 16) - 1u : 120u;
@@ -1456,9 +1545,14 @@ static lcd::SpecLaunch spec_launch(const Step &s) {
     l.validate_blocks = s.p.spec_vblocks;
     l.events16 = s.p.ev16 ? s.d->events16 : nullptr;
     l.cost_cuts = (o.path_flags & LC_PATH_SPEC_COST) != 0;
-    l.prio = !(o.path_flags & LC_PATH_SPEC_NOPRIO);
+    // Issue priority by progress helps a launch that has the device to
+    // itself (its laggards run ahead); beside another step's launch, whose
+    // fresh blocks would all outrank this one's tail, wave age alone measured
+    // better (C2, 200 overlapping steps: 0.1735 against 0.1796 ms per step;
+    // one search at a time 0.2130 with it, 0.2568 without)
+    l.prio = !(o.path_flags & LC_PATH_SPEC_NOPRIO) && !(s.lu && s.lu->overlap);
     l.vfirst = s.p.spec_vfirst;
-    l.fin = s.p.exact ? c->spec_fin : nullptr;
+    l.fin = s.p.exact ? s.L->spec_fin : nullptr;
     l.stage = !(o.path_flags & LC_PATH_SPEC_NOSTAGE);
     return l;
 }
@@ -1473,11 +1567,11 @@ static int launch_register_tier(Step &s, const lcd::Args &a0, const lcd::Args *d
     const int64_t K = s.K;
     if (p.side_validate) {
         HIPCHK(hipEventRecord(c->vin, c->stream));
-        HIPCHK(hipStreamWaitEvent(c->vstream, c->vin, 0));
+        HIPCHK(hipStreamWaitEvent(c->stream1, c->vin, 0));
         lcd::Args av = s.a;
         av.n_order = (int32_t)K;
-        HIPCHK(lcd::launch_validate(av, c->vstream, p.gen_validate));
-        HIPCHK(hipEventRecord(c->vdone, c->vstream));
+        HIPCHK(lcd::launch_validate(av, c->stream1, p.gen_validate));
+        HIPCHK(hipEventRecord(c->vdone, c->stream1));
     }
     // (et0 only where its time is read: each recorded event costs the stream
     // a few microseconds between kernels)
@@ -1487,9 +1581,9 @@ static int launch_register_tier(Step &s, const lcd::Args &a0, const lcd::Args *d
         HIPCHK(lcd::launch_segments(seg_args(s, grid), grid, c->stream));
         if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
     } else if (p.spec) {
-        HIPCHK(lcd::launch_spec(a0, dargs, spec_launch(s), c->stream));
-        c->spec_parity ^= 1;
-        if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
+        HIPCHK(lcd::launch_spec(a0, dargs, spec_launch(s), s.q));
+        s.L->spec_parity ^= 1;
+        if (!p.async) HIPCHK(hipEventRecord(c->et0, s.q));
     } else if (K > 0 && !s.d->table) {
         HIPCHK(lcd::launch_t0(a0, dargs, p.g0, p.t0_wide, c->stream, s.ticket_base));
         if (!p.async) HIPCHK(hipEventRecord(c->et0, c->stream));
@@ -1512,7 +1606,18 @@ static int finish_async(const Step &s, lc_stats *st, bool *enqueued) {
     // (the span's end, ea1, is recorded by dev_wait after the last
     // enqueued step: one timing event per step cost the stream a few
     // microseconds between searches)
-    HIPCHK(hipEventRecord(c->ring[c->async_seq % 4], c->stream));
+    if (s.lu && s.lu->dst) {
+        // records that went into the lane's block: out to the caller's
+        // buffer, behind the step that was given that buffer before (the
+        // wait stands after the searches' launches, so it delays neither)
+        if (s.lu->after) HIPCHK(hipStreamWaitEvent(s.q, s.lu->after, 0));
+        HIPCHK(hipMemcpyAsync(s.lu->dst, s.L->rec, s.lu->n * 8, hipMemcpyDeviceToHost, s.q));
+    }
+    HIPCHK(hipEventRecord(c->ring[c->async_seq % 4], s.q));
+    if (s.lu && s.lu->overlap) {
+        ++c->run_n;
+        c->lane1_live |= s.lu->lane == 1;
+    }
     c->ea1_pending = true;
     ++c->async_seq;
     ++c->n_async;
@@ -1657,19 +1762,33 @@ static void fill_stats(const Step &s, lc_stats *st) {
 // in c's own device arrays (r unused).  allow_async: a step that is T0 alone
 // is only enqueued (*enqueued = true; errors surface at the next wait).
 // What runs is plan_step's choice (step_plan.hpp); this is the order it runs in.
+// lu: an overlapping step of lc_check_node_async and its lane (plan_lane's
+// choice, lane_plan.hpp); any other step runs on lane 0, behind everything
+// enqueued on either lane before it.
 static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mode, bool allow_async, int64_t key0,
-                      lc_stats *st, bool *enqueued = nullptr, int64_t res_off = 0) {
+                      lc_stats *st, bool *enqueued = nullptr, int64_t res_off = 0, const LaneUse *lu = nullptr) {
     lc::Range range("lincheck: search");
     if (enqueued) *enqueued = false;
     const auto t0 = std::chrono::steady_clock::now();
     HIPCHK(hipSetDevice(c->device));
     const int64_t K = d->n_keys;
     if (K > 0x7FFFFFFF) return lc::fail(LC_E_INVALID, "lc_check_device: too many keys");
+    const bool overlap = lu && lu->overlap;
+    if (!overlap) LCCHK(join_lanes(c));
     LCCHK(ensure_capacity(c, K));
     Step s{c, d, r, mode, K, t0};
+    s.lu = lu;
+    s.L = &c->lane[overlap ? lu->lane : 0];
+    s.q = s.L->stream;
     step_args(s, key0, res_off);
     s.p = lc::plan_step(step_in(s, allow_async));
     const lc::StepPlan &p = s.p;
+    if (overlap && !(p.async && p.spec))
+        return lc::fail(LC_E_DEVICE, "lc_check_node_async: an overlapping step left the speculative segments");
+    if (overlap && lu->lane == 1 && c->lane1_wait_start) {  // lane 0's set-up of this run, once
+        HIPCHK(hipStreamWaitEvent(s.q, c->run_start, 0));
+        c->lane1_wait_start = false;
+    }
     s.a.strict = p.strict ? 1 : 0;
     if (s.analyzer && K > 0 && !p.wgl_only) HIPCHK(hipMemsetAsync(s.analyzer, LC_ALGO_LINEAR, (size_t)K, c->stream));
     if (p.wgl_only) return search_wgl(s, st);
@@ -1681,15 +1800,21 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
     if (p.async) s.a.err = c->counters + ERR_RING + 2 * (int)(c->async_seq % 4);
     if (p.split) LCCHK(ensure_segments(c, K));
     if (p.spec) LCCHK(ensure_spec_ws(s));
-    if (!p.ev16) LCCHK(ensure_ev32(c, d));
+    if (!p.ev16) LCCHK(ensure_ev32(c, d, s.q));
     lcd::Args a0{}, *dargs = nullptr;  // (zeroed padding too: args_slot compares the bytes)
     LCCHK(t0_args(s, &a0));
-    LCCHK(args_slot(c, a0, &dargs));
+    LCCHK(args_slot(*s.L, a0, &dargs));
     // timing events only where their times are read (each recorded event
     // costs the stream a few microseconds between kernels): an enqueued step
     // is timed by the span ea0 .. ea1 alone
     if (!p.async) HIPCHK(hipEventRecord(c->e0, c->stream));
-    if (p.async && c->n_async == 0) HIPCHK(hipEventRecord(c->ea0, c->stream));
+    if (p.async && c->n_async == 0) HIPCHK(hipEventRecord(c->ea0, s.q));
+    if (overlap && lu->lane == 0 && c->run_n == 0) {
+        // a run of overlapping steps begins: lane 1 starts behind what lane 0
+        // holds so far, this step's set-up included
+        HIPCHK(hipEventRecord(c->run_start, s.q));
+        c->lane1_wait_start = true;
+    }
     LCCHK(launch_register_tier(s, a0, dargs));
     if (p.async) return finish_async(s, st, enqueued);
     if (K > 0 && !p.t0_step) LCCHK(run_set_tiers(s));
@@ -1715,6 +1840,9 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
 static int dev_wait(Dev *c, int *n_async, float *span_ms) {
     lc::Range range("lincheck: wait");
     HIPCHK(hipSetDevice(c->device));
+    // lane 0 behind lane 1: the span's end below is the later lane's, and
+    // the one synchronisation covers both
+    LCCHK(join_lanes(c));
     if (c->ea1_pending) HIPCHK(hipEventRecord(c->ea1, c->stream));
     c->ea1_pending = false;
     HIPCHK(hipMemcpyAsync(c->hctl + 6, c->counters + 4, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -1916,7 +2044,7 @@ extern "C" int lc_wait_step(lc_ctx *c, int back) {
         HIPCHK(hipSetDevice(d->device));
         int r;
         if (back < 0 || back >= 4 || (uint64_t)back >= d->async_seq) {
-            HIPCHK(hipStreamSynchronize(d->stream));  // no such step on record: everything
+            LCCHK(drain_lanes(d));  // no such step on record: everything
             r = take_ring(d, 0xFu, -1, d->stream);
         } else {
             // Errors of the finished step surface here (include/lincheck.h):
@@ -1982,7 +2110,7 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
 // padding past the shard's n keys is zeroed.
 static int node_buffers(lc_ctx *x, Dev *c, int64_t n, int64_t block) {
     if (block > c->node_cap || !c->send) {
-        if (c->n_async) HIPCHK(hipStreamSynchronize(c->stream));  // an enqueued step may still write them
+        if (c->n_async) LCCHK(drain_lanes(c));  // an enqueued step may still write them
         dfree(c->send);
         dfree(c->node);
         HIPCHK(dalloc(&c->send, (size_t)std::max<int64_t>(block, 1)));
@@ -2017,8 +2145,21 @@ struct RecOff {
 // A node step's error return: the copies out of the caller's arrays are waited for.
 static int drained(Dev *d, int e) {
     (void)hipStreamSynchronize(d->cstream);
+    (void)hipStreamSynchronize(d->stream1);
     (void)hipStreamSynchronize(d->stream);
+    d->lane1_live = d->lane1_wait_start = false;
+    d->run_n = 0;
     return e;
+}
+
+// An overlapping step's record block on its lane (grown on demand), the
+// padding past the shard's n keys zeroed: the search writes its records
+// there, and they are copied out behind it (finish_async).
+static int lane_records(Dev *c, Lane &L, int64_t n, int64_t block) {
+    LCCHK(grow_dev(c, L.rec, L.rec_cap, std::max<int64_t>(block, 1)));
+    if (block > n) HIPCHK(hipMemsetAsync(L.rec + n, 0, (size_t)(block - n) * 8, L.stream));
+    c->rec_out = L.rec;
+    return LC_OK;
 }
 
 static int node_check_args(lc_ctx *c, int64_t n_keys, int64_t block) {
@@ -2138,13 +2279,22 @@ extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64
     return LC_OK;
 }
 
+// What dev_search will plan for a node step whose results stay in the
+// context (plan_lane decides from it before the search is enqueued).
+static lc::StepPlan node_step_plan(Dev *c, const DevBatch *d) {
+    const Step s{c, d, nullptr, RES_CTX, d->n_keys, {}};
+    return lc::plan_step(step_in(s, true));
+}
+
 // The pipelined form of lc_check_node.  A register-tier step (every key fits
 // the register lattice, no probe counting, one upload, records to page-locked
 // memory) is only enqueued: its upload goes into the staging slot the step
-// two back used (once that step is done) on the copy stream, its search waits
-// for that upload on the search stream, and the records are downloaded into
-// `node` behind the search.  So step i + 1's host-to-device copy overlaps step
-// i's search, and the host enqueues ahead instead of waiting between steps.
+// three back used (once that step is done) on the copy stream, its search
+// follows that upload on one of the two search lanes, and the records land
+// in `node` with the search or behind it.  So step i + 2's host-to-device
+// copy overlaps the searches of steps i and i + 1, step i + 1's workgroups
+// take the slots step i's finished blocks free (lane_plan.hpp), and the host
+// enqueues ahead instead of waiting between steps.
 // Anything else runs as lc_check_node.
 extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, uint64_t *node, lc_stats *st) {
     lc::Range range("lc_check_node_async");
@@ -2167,7 +2317,11 @@ extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, 
             rc = prepare_batch(c, b, &sh, &src);
             if (rc) return rc;
             if (sh.t0_only) {
-                const int s = (int)(d->pipe_next % Dev::PIPE);
+                // where the step runs is plan_lane's choice (lane_plan.hpp);
+                // its staging slot follows from the sequence number alone
+                lc::LaneIn li;
+                li.seq = d->pipe_next;
+                const int s = lc::plan_lane(li).slot;
                 if (!d->pipe[s]) {
                     d->pipe[s] = new (std::nothrow) DevBatch();
                     if (!d->pipe[s]) return lc::fail(LC_E_NOMEM, "lc_check_node_async: out of memory");
@@ -2179,43 +2333,78 @@ extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, 
                         HIPCHK(hipEventCreateWithFlags(&d->pipe_ready[s], hipEventDisableTiming));
                     }
                 }
-                // the step that last read this slot has finished (at most one
-                // other step stays in flight), so its buffers may be rewritten
-                // or regrown.  Its end is the ring event its search recorded:
-                // a marker of its own after every step cost the stream ~5 us
-                // between consecutive searches (a system-scope fence each).
+                // the step that last read this slot (three back) has finished
+                // -- at most two other steps stay in flight, one on each lane
+                // -- so its buffers may be rewritten or regrown.  Its end is
+                // the ring event its search recorded: a marker of its own
+                // after every step cost the stream ~5 us between consecutive
+                // searches (a system-scope fence each).
                 // (A ring slot re-recorded since by a later step only makes
                 // this wait for that later step.)
                 if (d->pipe_busy[s]) HIPCHK(hipEventSynchronize(d->ring[d->pipe_seq[s] % 4]));
-                // One rank: the search writes the records straight into the
-                // caller's page-locked buffer (device-mapped), so no download
-                // follows it; with a communicator they go through HBM for the
-                // all-gather.
-                uint64_t *dnode = nullptr;
-                const bool direct = !c->comm && !(c->o.path_flags & LC_PATH_NODE_STAGED) &&
-                                    hipHostGetDevicePointer((void **)&dnode, node, 0) == hipSuccess && dnode;
-                if (direct) {
-                    if (block > K) std::memset(node + K, 0, (size_t)(block - K) * 8);
-                    d->rec_out = dnode;
-                } else {
-                    rc = node_buffers(c, d, K, block);
-                    if (rc) return rc;
-                }
-                RecOff rec_off{d};
+                d->pipe_busy[s] = false;
                 rc = upload_into(d, b, d->pipe[s], sh, sh.host_checked, src, false, d->cstream);
                 if (rc) return drained(d, rc);
                 HIPCHK(hipEventRecord(d->pipe_ready[s], d->cstream));
-                // The host waits for the upload (the previous step's search
-                // is running meanwhile) and then enqueues the search: no
+                // The lane, and how the records reach `node`.  One rank: the
+                // search writes them straight into the caller's page-locked
+                // buffer (device-mapped), so no download follows it -- unless
+                // a step still in flight was given that buffer too and this
+                // step may overlap it: then they go through the lane's block
+                // in HBM and are copied out behind that step's end, so the
+                // buffer ends up with the latest step's records.  With a
+                // communicator they go through HBM for the all-gather.
+                uint64_t *dnode = nullptr;
+                li.mapped = hipHostGetDevicePointer((void **)&dnode, node, 0) == hipSuccess && dnode;
+                if (!li.mapped) (void)hipGetLastError();
+                const lc::StepPlan stp = node_step_plan(d, d->pipe[s]);
+                li.run_n = d->run_n;
+                li.async = stp.async; li.spec = stp.spec; li.split = stp.split;
+                li.waves = K * stp.segs;
+                li.resident_waves = (int64_t)d->cu_count * 4 * LC_SPEC8_WAVES;
+                li.comm = c->comm != nullptr;
+                li.path_flags = c->o.path_flags;
+                li.lo = (uint64_t)(uintptr_t)node;
+                li.hi = li.lo + (uint64_t)std::max<int64_t>(block, 1) * 8;
+                for (int t = 0; t < Dev::PIPE; ++t) {
+                    if (t == s || !d->pipe_busy[t]) continue;
+                    if (hipEventQuery(d->ring[d->pipe_seq[t] % 4]) == hipSuccess) {
+                        d->pipe_busy[t] = false;
+                        continue;
+                    }
+                    (void)hipGetLastError();
+                    lc::LaneIn::Flight &f = li.flight[li.n_flight++];
+                    f.seq = d->pipe_seq[t]; f.lo = d->pipe_lo[t]; f.hi = d->pipe_hi[t];
+                }
+                const lc::LanePlan lp = lc::plan_lane(li);
+                LaneUse lu;
+                lu.lane = lp.lane;
+                lu.overlap = lp.overlap;
+                if (lp.direct) {
+                    if (block > K) std::memset(node + K, 0, (size_t)(block - K) * 8);
+                    d->rec_out = dnode;
+                } else if (lp.overlap) {
+                    rc = lane_records(d, d->lane[lp.lane], K, block);
+                    if (rc) return drained(d, rc);
+                    lu.dst = node;
+                    lu.n = (size_t)block;
+                    lu.after = lp.after >= 0 ? d->ring[lp.after % 4] : nullptr;
+                } else {
+                    rc = node_buffers(c, d, K, block);
+                    if (rc) return drained(d, rc);
+                }
+                RecOff rec_off{d};
+                // The host waits for the upload (the steps before are
+                // searching meanwhile) and then enqueues the search: no
                 // cross-stream wait on the device, whose latency sat between
                 // consecutive searches (C2 0.3415 -> 0.3365 ms per step).  It
                 // also frees the context's staging copy of pageable events.
                 HIPCHK(hipEventSynchronize(d->pipe_ready[s]));
                 lc_result none{};
                 bool enq = false;
-                rc = dev_search(d, d->pipe[s], &none, RES_CTX, true, 0, st, &enq);
+                rc = dev_search(d, d->pipe[s], &none, RES_CTX, true, 0, st, &enq, 0, &lu);
                 if (rc) return drained(d, rc);
-                if (direct) {
+                if (lp.direct || lu.dst) {
                     d->node_n = 0;  // the records are in `node` only (lc_node_records has none)
                 } else {
                     rc = gather_node(c, d, block);
@@ -2226,6 +2415,8 @@ extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, 
                 }
                 d->pipe_busy[s] = enq;
                 d->pipe_seq[s] = d->async_seq - 1;
+                d->pipe_lo[s] = li.lo;
+                d->pipe_hi[s] = li.hi;
                 ++d->pipe_next;
                 if (enq) return 1;
                 HIPCHK(hipStreamSynchronize(d->stream));  // not reached for a register-tier batch
@@ -2277,6 +2468,7 @@ extern "C" int lc_node_records(lc_ctx *c, uint64_t *node, int64_t n) {
     if (n > d->node_n) return lc::fail(LC_E_INVALID, "lc_node_records: %lld records asked, %lld gathered",
                                        (long long)n, (long long)d->node_n);
     HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
     if (n) HIPCHK(hipMemcpyAsync(node, d->node, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
     return LC_OK;
@@ -2289,6 +2481,7 @@ extern "C" int lc_set_check(lc_ctx *c, const lc_set_batch *b, lc_set_result *r) 
     std::lock_guard<std::mutex> g(c->mu);
     Dev *d = c->dev[0];
     HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
     return lcs::set_check(&d->setdev, d->stream, c->o.path_flags, b, r);
 }
 
@@ -2305,6 +2498,7 @@ extern "C" int lc_perf_check(lc_ctx *c, const lc_perf_batch *b, const lc_perf_op
     std::lock_guard<std::mutex> g(c->mu);
     Dev *d = c->dev[0];
     HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
     return lcp::perf_check(&d->perfdev, d->stream, b, o, r);
 }
 

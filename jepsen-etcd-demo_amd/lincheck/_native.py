@@ -29,6 +29,7 @@ LC_PATH_WGL_EV_HBM = 0x2000  # ABI 11
 LC_PATH_SPEC_NOSTAGE = 0x1000
 LC_PATH_SET_HBM = 0x4000  # ABI 12: lc_set_check, every key through the HBM tier
 LC_PATH_SET_DIRECT = 0x8000  # ABI 12: k_set_mark without its LDS tile
+LC_PATH_NODE_SERIAL = 0x10000  # lc_check_node_async: one search at a time (A/B against the two search lanes)
 LC_T0_PATH_NONE, LC_T0_PATH_LATTICE, LC_T0_PATH_SPEC, LC_T0_PATH_SEGMENTS = 0, 1, 2, 3
 T0_PATH_NAMES = {0: "none", 1: "k_search_lattice", 2: "k_spec", 3: "k_search_segments"}
 LC_DEV_RESULT, LC_DEV_ASYNC = 1, 2
