@@ -897,6 +897,101 @@ int  lc_perf_hist_view(const lc_perf_hist *h, lc_perf_history *out);
 const char *lc_perf_hist_name(const lc_perf_hist *h, int64_t i);
 void lc_perf_hist_free(lc_perf_hist *h);
 
+/* ---- incremental check: a resident search fed as the history grows ------------ */
+/* A Jepsen run writes its history over minutes or hours.  A stream keeps every
+ * key's register-tier search state on the device between calls, so each call
+ * searches only what is new and a stale read is reported while the test still
+ * runs.  Additive to ABI 13: own structs and entry
+ * points, nothing above changes.
+ *
+ * Rows mode (lc_stream_append): the caller hands over history rows as they are
+ * written.  knossos.history/complete makes an invocation's event depend on its
+ * completion (a read learns its value from its :ok, a :fail removes the pair,
+ * an :info or a later invoke of the same process leaves the op pending
+ * forever), so per key the rows from the first invoke whose fate is still open
+ * are held back; everything before it -- the key's DECIDED PREFIX -- is turned
+ * into event words (the words lc_pack would give) and searched.  After any
+ * call a key is invalid exactly when its decided prefix holds the :ok that
+ * cannot be linearized; it stays invalid, with that event's ordinal.
+ * lc_stream_finish decides every held row (ops still open are pending forever)
+ * and after it every key's valid, cause and fail_event equal lc_pack +
+ * lc_check_batch on the concatenated rows, whatever the split into calls.
+ *   A completion with no open invocation, or an :invoke the model cannot step,
+ * makes that key :unknown with LC_CAUSE_ERROR from then on (as lc_pack does
+ * for the whole key) -- even if it was reported invalid earlier.  Rows with
+ * neither a key nor an integer process (the nemesis) are skipped.  A keyless
+ * row of an integer process, an LC_F_TXN row or a bad :type / :f code refuses
+ * the whole call and leaves the stream as it was.
+ *   The register tier holds 10 pending ops and 32 register states.  A key
+ * whose next invoke would pass either is DEFERRED: from that event on its
+ * words stay on the host, and lc_stream_finish checks the key once, from its
+ * first event, through lc_check_batch with the context's budget.
+ *
+ * Events mode (lc_stream_push): the caller packs chunks itself.  Chunk key k
+ * continues stream key key_ids[k] (new ids are new keys, in order of first
+ * appearance); its words continue the key's earlier ones -- window slots and
+ * state ids carry on across chunks, which is the caller's contract -- while
+ * trans / trans_off / key_states / key_width (both required) are the chunk's
+ * own.  The device validates the words; a key with malformed ones becomes
+ * LC_CAUSE_ERROR and the call returns LC_E_INVALID naming it, the other keys
+ * having advanced.  A chunk with a key_width above 10, a key_states above 32 or
+ * a table is refused whole (LC_E_UNSUPPORTED).
+ *
+ * A stream is in one mode, fixed by its first call (mixing: LC_E_INVALID).  It
+ * counts no probes and no peaks, and returns no final configs: to render the
+ * counterexample of a key found invalid, run the ordinary checker on that
+ * key's sub-history. */
+typedef struct lc_stream lc_stream;  /* library-owned */
+
+typedef struct lc_stream_update {
+    int64_t        n_keys;      /* keys of the stream so far                          */
+    int64_t        events;      /* event words searched on the device in this call    */
+    int64_t        rows_held;   /* rows held back, over all keys (rows mode)           */
+    int64_t        n_deferred;  /* keys deferred to lc_stream_finish so far            */
+    int64_t        n_invalid;   /* keys that turned invalid in this call ...           */
+    const int64_t *invalid;     /* ... their key indices, ascending (borrowed: valid
+                                   until the stream's next call)                     */
+} lc_stream_update;
+
+#define LC_STREAM_REC_WORDS 1360  /* a key's device record, 32-bit words (csrc/stream_plan.hpp) */
+
+/* ctx NULL: a packer-only stream (rows mode without a device: the accessors
+ * below work, lc_stream_results does not).  opts NULL: cas-register.  A
+ * context of several devices or with a communicator, or one whose budget is
+ * below 16 x 64 x 32 (where the register tier's sets are exact), is refused
+ * with LC_E_UNSUPPORTED; so is LC_MODEL_MULTI_REGISTER.  The context must
+ * outlive the stream. */
+int  lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream **out);
+int  lc_stream_append(lc_stream *s, const lc_history *rows, lc_stream_update *u);
+int  lc_stream_push(lc_stream *s, const lc_batch *chunk, const int64_t *key_ids, lc_stream_update *u);
+int  lc_stream_finish(lc_stream *s, lc_stream_update *u);
+/* valid, fail_event and cause of every key so far, in key-index order (the
+ * other arrays of r are not touched).  Before lc_stream_finish a key that is
+ * neither invalid nor in error is LC_VALID: nothing searched so far refutes it. */
+int  lc_stream_results(lc_stream *s, lc_result *r);
+/* Keys in order of first appearance; returns their count (out may be NULL). */
+int64_t lc_stream_keys(const lc_stream *s, int64_t *out);
+/* Key i's counts: out4 = events emitted (its decided prefix), rows held back,
+ * the event ordinal it was deferred at (-1: it is not), events searched on the
+ * device. */
+int  lc_stream_key_events(const lc_stream *s, int64_t i, int64_t *out4);
+/* History row (counted over every row appended, from 0) of event j of key i. */
+int64_t lc_stream_event_row(const lc_stream *s, int64_t i, int64_t j);
+/* Rows mode: key i's emitted event words (32-bit form) / its transition
+ * descriptors; returns the count and writes at most cap. */
+int64_t lc_stream_key_words(const lc_stream *s, int64_t i, uint32_t *out, int64_t cap);
+int64_t lc_stream_key_trans(const lc_stream *s, int64_t i, uint32_t *out, int64_t cap);
+/* Register value of state id st of key i (state 0 = nil -> *is_nil = 1). */
+int  lc_stream_state_value(const lc_stream *s, int64_t i, uint32_t st, int64_t *value, int *is_nil);
+/* Why key i is in error (NULL when it is not; borrowed). */
+const char *lc_stream_key_error(const lc_stream *s, int64_t i);
+/* Diagnostics: key i's device record (LC_STREAM_REC_WORDS words), and the
+ * times of the last call, ms: [0] host packing, [1] upload, [2] k_stream,
+ * [3] readback (device events). */
+int  lc_stream_record(lc_stream *s, int64_t i, uint32_t *out);
+int  lc_stream_last_timing(const lc_stream *s, double *out_ms4);
+void lc_stream_close(lc_stream *s);
+
 #ifdef __cplusplus
 }
 #endif

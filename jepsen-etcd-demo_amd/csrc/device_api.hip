@@ -32,8 +32,10 @@
 #include "device_search.hpp"
 #include "device_perf.hpp"
 #include "device_set.hpp"
+#include "device_stream.hpp"
 #include "step_plan.hpp"
 #include "lane_plan.hpp"
+#include "stream_plan.hpp"
 
 #define HIPCHK(expr)                                                                       \
     do {                                                                                   \
@@ -2506,4 +2508,185 @@ extern "C" int lc_perf_last_timing(lc_ctx *c, double *out_ms) {
     if (!c || !out_ms) return lc::fail(LC_E_INVALID, "lc_perf_last_timing: null argument");
     std::lock_guard<std::mutex> g(c->mu);
     return lcp::perf_last_timing(c->dev[0]->perfdev, out_ms);
+}
+
+// ---- a resident search (lc_stream_*; device_lattice.hip k_stream) ---------------
+// host_stream.cpp owns the stream (its packer, verdicts and C entry points);
+// this is its device half: the per-key records and one launch per call.
+
+static_assert(sizeof(lcst::Item) == sizeof(lcd::StreamItem) && offsetof(lcst::Item, ns) == offsetof(lcd::StreamItem, ns),
+              "lcst::Item is lcd::StreamItem");
+
+struct lcst::StreamDev {
+    lc_ctx *ctx = nullptr;
+    uint32_t *rec = nullptr;   // STREAM_REC_WORDS per key
+    int64_t rec_cap = 0;       // keys
+    char *din = nullptr, *hin = nullptr;  // a call's items, transitions, words: device, pinned host
+    size_t in_cap = 0;
+    uint32_t *dout = nullptr, *hout = nullptr;  // the dead list
+    size_t out_cap = 0;        // words
+    hipEvent_t ev[4] = {};
+    float ms[3] = {0, 0, 0};
+};
+
+namespace {
+constexpr size_t STREAM_OUT_HEAD = 63;  // dead keys read back with the count, in one copy
+size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+int stream_grow(lcst::StreamDev *s, Dev *d, int64_t n_keys, size_t in_bytes, size_t out_words) {
+    if (n_keys > s->rec_cap) {
+        const int64_t cap = std::max<int64_t>({n_keys, 2 * s->rec_cap, 64});
+        uint32_t *nr = nullptr;
+        HIPCHK(dalloc(&nr, (size_t)cap * lc::STREAM_REC_WORDS));
+        const size_t old = (size_t)s->rec_cap * lc::STREAM_REC_WORDS * 4, all = (size_t)cap * lc::STREAM_REC_WORDS * 4;
+        hipError_t e = hipSuccess;
+        if (old) e = hipMemcpyAsync(nr, s->rec, old, hipMemcpyDeviceToDevice, d->stream);
+        if (e == hipSuccess) e = hipMemsetAsync((char *)nr + old, 0, all - old, d->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+        if (e != hipSuccess) {
+            dfree(nr);
+            return lc::fail(LC_E_DEVICE, "lc_stream: growing the records failed: %s", hipGetErrorString(e));
+        }
+        dfree(s->rec);
+        s->rec = nr;
+        s->rec_cap = cap;
+    }
+    if (in_bytes > s->in_cap) {
+        const size_t cap = std::max<size_t>(in_bytes * 2, 1 << 16);
+        if (s->din) (void)hipFree(s->din);
+        if (s->hin) (void)hipHostFree(s->hin);
+        s->din = s->hin = nullptr;
+        s->in_cap = 0;
+        HIPCHK(hipMalloc((void **)&s->din, cap));
+        HIPCHK(hipHostMalloc((void **)&s->hin, cap, hipHostMallocDefault));
+        s->in_cap = cap;
+    }
+    if (out_words > s->out_cap) {
+        const size_t cap = std::max<size_t>(out_words * 2, 1024);
+        dfree(s->dout);
+        if (s->hout) (void)hipHostFree(s->hout);
+        s->hout = nullptr;
+        s->out_cap = 0;
+        HIPCHK(dalloc(&s->dout, cap));
+        HIPCHK(hipHostMalloc((void **)&s->hout, cap * 4, hipHostMallocDefault));
+        s->out_cap = cap;
+    }
+    return LC_OK;
+}
+}  // namespace
+
+int lcst::stream_dev_open(lc_ctx *c, StreamDev **out) {
+    if (c->n_dev != 1 || c->comm)
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: a stream needs a context of one device and no communicator");
+    if (c->o.max_configs < lc::STREAM_MIN_BUDGET)
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: budget %llu is below %llu, where the register tier's sets are exact",
+                        (unsigned long long)c->o.max_configs, (unsigned long long)lc::STREAM_MIN_BUDGET);
+    std::lock_guard<std::mutex> g(c->mu);
+    HIPCHK(hipSetDevice(c->dev[0]->device));
+    StreamDev *s = new StreamDev;
+    s->ctx = c;
+    for (hipEvent_t &e : s->ev) {
+        hipError_t r = hipEventCreate(&e);
+        if (r != hipSuccess) {
+            for (hipEvent_t &x : s->ev)
+                if (x) (void)hipEventDestroy(x);
+            delete s;
+            return lc::fail(LC_E_DEVICE, "lc_stream_open: hipEventCreate failed: %s", hipGetErrorString(r));
+        }
+    }
+    *out = s;
+    return LC_OK;
+}
+
+void lcst::stream_dev_close(StreamDev *s) {
+    if (!s) return;
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    Dev *d = s->ctx->dev[0];
+    (void)hipSetDevice(d->device);
+    (void)hipStreamSynchronize(d->stream);
+    dfree(s->rec);
+    dfree(s->dout);
+    if (s->din) (void)hipFree(s->din);
+    if (s->hin) (void)hipHostFree(s->hin);
+    if (s->hout) (void)hipHostFree(s->hout);
+    for (hipEvent_t e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+}
+
+void lcst::stream_dev_timing(const StreamDev *s, double *out3) {
+    for (int i = 0; i < 3; ++i) out3[i] = s->ms[i];
+}
+
+int lcst::stream_dev_record(StreamDev *s, int64_t key, uint32_t *out) {
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    if (key < 0 || key >= s->rec_cap) return lc::fail(LC_E_INVALID, "lc_stream_record: key %lld has no record", (long long)key);
+    Dev *d = s->ctx->dev[0];
+    HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
+    HIPCHK(hipMemcpyAsync(out, s->rec + (size_t)key * lc::STREAM_REC_WORDS, lc::STREAM_REC_WORDS * 4, hipMemcpyDeviceToHost,
+                          d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return LC_OK;
+}
+
+int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
+                          uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
+                          std::vector<Dead> *dead) {
+    dead->clear();
+    s->ms[0] = s->ms[1] = s->ms[2] = 0;
+    if (n_items <= 0) return LC_OK;
+    if (n_items > (int64_t)1 << 30 || n_ev > 0xFFFFFFFFull || n_trans > 0xFFFFFFFFull)
+        return lc::fail(LC_E_INVALID, "lc_stream: too much for one call");
+    // every index a wave follows, checked before the launch
+    for (int64_t i = 0; i < n_items; ++i) {
+        const Item &it = items[i];
+        if (it.key < 0 || it.key >= n_keys || it.ev_b > it.ev_e || it.ev_e > n_ev || it.tr_b > n_trans ||
+            it.ntr > n_trans - it.tr_b)
+            return lc::fail(LC_E_INVALID, "lc_stream: work item %lld is out of range (internal error)", (long long)i);
+    }
+    lc_ctx *c = s->ctx;
+    std::lock_guard<std::mutex> g(c->mu);
+    Dev *d = c->dev[0];
+    HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
+    const size_t o_items = 0, o_trans = up16((size_t)n_items * sizeof(Item)),
+                 o_ev = o_trans + up16((size_t)n_trans * 4), in_bytes = o_ev + up16((size_t)n_ev * 2);
+    const size_t out_words = 1 + 4 * (size_t)n_items;
+    LCCHK(stream_grow(s, d, n_keys, in_bytes, out_words));
+    std::memcpy(s->hin + o_items, items, (size_t)n_items * sizeof(Item));
+    if (n_trans) std::memcpy(s->hin + o_trans, trans, (size_t)n_trans * 4);
+    if (n_ev) std::memcpy(s->hin + o_ev, ev16, (size_t)n_ev * 2);
+    HIPCHK(hipEventRecord(s->ev[0], d->stream));
+    HIPCHK(hipMemcpyAsync(s->din, s->hin, in_bytes, hipMemcpyHostToDevice, d->stream));
+    HIPCHK(hipMemsetAsync(s->dout, 0, 4, d->stream));
+    HIPCHK(hipEventRecord(s->ev[1], d->stream));
+    lcd::StreamArgs a{};
+    a.items = (const lcd::StreamItem *)(s->din + o_items);
+    a.trans = (const uint32_t *)(s->din + o_trans);
+    a.events16 = (const uint16_t *)(s->din + o_ev);
+    a.rec = s->rec;
+    a.out = s->dout;
+    a.n_items = (int32_t)n_items;
+    a.init_state = init_state;
+    HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(n_items, 8192), d->stream));
+    HIPCHK(hipEventRecord(s->ev[2], d->stream));
+    const size_t head = std::min<size_t>(out_words, 1 + 4 * STREAM_OUT_HEAD);
+    HIPCHK(hipMemcpyAsync(s->hout, s->dout, head * 4, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipEventRecord(s->ev[3], d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    const size_t n_dead = s->hout[0];
+    if (n_dead > (size_t)n_items) return lc::fail(LC_E_DEVICE, "lc_stream: the dead list holds more keys than the launch had");
+    if (1 + 4 * n_dead > head) {
+        HIPCHK(hipMemcpyAsync(s->hout + head, s->dout + head, (1 + 4 * n_dead - head) * 4, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipStreamSynchronize(d->stream));
+    }
+    for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&s->ms[i], s->ev[i], s->ev[i + 1]);
+    dead->resize(n_dead);
+    for (size_t i = 0; i < n_dead; ++i) {
+        const uint32_t *o = s->hout + 1 + 4 * i;
+        (*dead)[i] = Dead{o[0], o[1], o[2], o[3]};
+    }
+    std::sort(dead->begin(), dead->end(), [](const Dead &x, const Dead &y) { return x.key < y.key; });
+    return LC_OK;
 }

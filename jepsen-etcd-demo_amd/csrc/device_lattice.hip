@@ -47,6 +47,7 @@
 #include "../../include/lincheck.h"
 #include "device_common.hpp"
 #include "device_search.hpp"
+#include "stream_plan.hpp"
 
 extern "C" __device__ uint32_t __ockl_wfred_add_u32(uint32_t);
 
@@ -946,6 +947,15 @@ struct LatWalk {
     uint32_t peak, probes;
 };
 
+// A walk's state between two events, for the resume form (k_stream; the
+// record's layout: stream_plan.hpp): in, where the walk starts; out, where
+// it stopped.  The lattice itself is W, or m.W when in_mem.
+struct LatResume {
+    uint32_t k_v, cap_v, b_v, slot_v, dense_v;  // per-op lanes, as in lattice_walk
+    uint32_t n, live;
+    bool in_mem, dirty;
+};
+
 // The register tier's event walk: events evp[0 .. nev) from the start word
 // `init` in lane 0 (a state mask; TAG: one 6-bit group per start state,
 // xfer_tag), transitions trp[t], t < ntr.  The unsegmented search
@@ -954,11 +964,17 @@ struct LatWalk {
 // FAST: no probe counting, no peak sizes and a budget no lattice can exceed
 // (>= 16 x 64 x 32 configs), so every size reduction and budget test folds
 // away -- the common case, and the bench's.
-template <int RM, bool FAST, bool TAG, class EvT>
+// RESUME: the walk starts from *rs and the lattice the caller loaded (W, or
+// m.W when rs->in_mem) instead of `init`, in the phase its pending count
+// belongs to (7 or more pending: the dense phase), and leaves its state in
+// *rs.  Event ordinals (fev) count from evp[0].
+template <int RM, bool FAST, bool TAG, class EvT, bool RESUME = false>
 __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, const EvT evp, const uint32_t nev,
                                              const uint32_t *const trp, const uint32_t ntr, uint32_t init,
-                                             const LatMem &m, uint64_t budget, bool want_peak, bool count) {
+                                             const LatMem &m, uint64_t budget, bool want_peak, bool count,
+                                             LatResume *rs = nullptr) {
     static_assert(!TAG || (FAST && RM == T0_RSMALL), "tagged words: closed sets on the compact lattice only");
+    static_assert(!RESUME || (FAST && !TAG && RM == T0_RSMALL), "resume: the compact FAST build only");
     const uint32_t lane = lane_id();
     auto ldesc = [&](uint32_t w, bool have) -> uint32_t {
         const uint32_t t = LC_EV_TRANS(w);
@@ -969,9 +985,11 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
         else return xfer_of(d);
     };
 
+    if constexpr (!RESUME) {
 #pragma unroll
-    for (int k = 0; k < RM; ++k) W[k] = 0;
-    if (lane == 0) W[0] = init;
+        for (int k = 0; k < RM; ++k) W[k] = 0;
+        if (lane == 0) W[0] = init;
+    }
     bool in_mem = false;   // lattice lives in m.W (9 or 10 ops pending)
     uint32_t k_v = 0, cap_v = 0, b_v = 0;  // lane j: transfer (k, cap, b) of the op at index j
     uint32_t m_v = 0;      // TAG: and its mask Mb
@@ -985,6 +1003,11 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
     uint32_t peak = 1, probes = 0;
     int status = 0;        // 1 invalid, 2 budget, 3 spill
     uint32_t fev = 0;
+    if constexpr (RESUME) {
+        in_mem = rs->in_mem;
+        k_v = rs->k_v; cap_v = rs->cap_v; b_v = rs->b_v; slot_v = rs->slot_v; dense_v = rs->dense_v;
+        n = rs->n; live = rs->live;
+    }
 
     // Event cursor: events arrive 64 at a time, one per lane; the next
     // chunk's words and descriptors are in flight while this one is searched.
@@ -1030,8 +1053,15 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
     //                  workspace; left after the :ok that brings n back to 6.
     uint32_t W0 = W[0];
     bool dirty = true;  // FAST: an op was invoked since the lattice was last closed
+    // RESUME with 7 or more pending: the first round skips the lane phase
+    // (stream_plan.hpp stream_resume_phase) and keeps the loaded lattice
+    [[maybe_unused]] bool dense_first = false;
+    if constexpr (RESUME) {
+        dirty = rs->dirty;
+        dense_first = n >= 7;
+    }
     for (uint32_t phase = 0; phase <= nev && e < lim; ++phase) {
-        while (e < lim) {
+        while (e < lim && !(RESUME && dense_first)) {
             T0_PROF_BEGIN
             const uint32_t evi = __builtin_amdgcn_readlane(ev, i);
             const uint32_t slot = LC_EV_SLOT(evi);
@@ -1100,9 +1130,12 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
             advance();
         }
         if (e >= lim) break;
-        W[0] = W0;
+        if (!(RESUME && dense_first)) {
+            W[0] = W0;
 #pragma unroll
-        for (int k = 1; k < RM; ++k) W[k] = 0u;
+            for (int k = 1; k < RM; ++k) W[k] = 0u;
+        }
+        if constexpr (RESUME) dense_first = false;
         while (e < lim) {
             T0_PROF_BEGIN
             const uint32_t evi = __builtin_amdgcn_readlane(ev, i);
@@ -1187,6 +1220,11 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
     W[0] = W0;
     out.in_mem = in_mem; out.slot_v = slot_v; out.live = live; out.n = n;
     out.status = status; out.fev = fev; out.peak = peak; out.probes = probes;
+    if constexpr (RESUME) {
+        rs->in_mem = in_mem;
+        rs->k_v = k_v; rs->cap_v = cap_v; rs->b_v = b_v; rs->slot_v = slot_v; rs->dense_v = dense_v;
+        rs->n = n; rs->live = live; rs->dirty = dirty;
+    }
 }
 
 // One key, unsegmented: K_DONE with its results written, or K_SPILL.
@@ -1446,6 +1484,127 @@ hipError_t launch_validate(const Args &a, hipStream_t s, bool general) {
     const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(a.n_order, 2048));
     if (general) hipLaunchKernelGGL(k_validate<true>, dim3(grid), dim3(64), 0, s, t);
     else hipLaunchKernelGGL(k_validate<false>, dim3(grid), dim3(64), 0, s, t);
+    return hipGetLastError();
+}
+
+// ---- A resident search (lc_stream_*) -------------------------------------------
+//
+// A history that is still being written is checked as it grows: each key's
+// walk state lives in a record in device memory (stream_plan.hpp) between
+// calls, and a call searches only the event words that are new.  One wave
+// per key with new words: load the record, validate the new words with the
+// slot-protocol words the record carries (the walk stays in bounds on any
+// input, but its verdict over malformed words means nothing), resume the
+// compact FAST walk where it stopped, store the record.  A key that died --
+// its set empty at an :ok, or its words malformed -- stores its header alone
+// and is appended to the launch's list; later launches leave it untouched.
+// Nothing waits on anything: the host reads the list back after the launch.
+__device__ __forceinline__ void stream_key(const StreamArgs &a, int32_t w, uint32_t *ws) {
+    using namespace lc;
+    const uint32_t lane = lane_id();
+    const LatMem m{ws, ws + T0_RMEM * 64, ws + 2 * T0_RMEM * 64};
+    const StreamItem it = a.items[w];
+    uint32_t *const r = a.rec + (size_t)it.key * STREAM_REC_WORDS;
+    const uint32_t hv = lane < STREAM_HDR_WORDS ? r[lane] : 0u;
+    auto H = [&](uint32_t i) { return (uint32_t)__builtin_amdgcn_readlane((int)hv, (int)i); };
+    if (H(STREAM_H_STATUS) != STREAM_LIVE) return;  // dead: the record stays as it is
+    const uint32_t nev = it.ev_e - it.ev_b;
+    if (!nev) return;
+    const uint32_t *const trp = a.trans + it.tr_b;
+    const EvSrc<true> evp{a.events16 + it.ev_b};
+    const uint32_t done = H(STREAM_H_DONE);
+
+    uint32_t pend[2] = {H(STREAM_H_PEND0), H(STREAM_H_PEND1)};
+    int32_t why = 0;
+    for (uint32_t base = 0; base < nev && !why; base += 64) {
+        const bool in = base + lane < nev;
+        const uint32_t wd = in ? evp[base + lane] : 0u;
+        why = validate_chunk<false, 2>(wd, in, trp, it.ntr, it.ns, 64u, pend);
+    }
+
+    uint32_t status = STREAM_LIVE, fail = 0;
+    LatResume rs{};
+    if (why) {
+        status = STREAM_ERROR;
+    } else {
+        uint32_t W[T0_RSMALL];
+        uint32_t *const la = r + STREAM_OFF_LANES, *const lat = r + STREAM_OFF_LATTICE;
+        if (H(STREAM_H_STARTED)) {
+            const uint32_t n0 = H(STREAM_H_N);
+            rs.n = n0 < T0_MAX_WIDTH ? n0 : T0_MAX_WIDTH;
+            rs.live = H(STREAM_H_LIVE);
+            rs.in_mem = stream_in_workspace(rs.n);
+            rs.dirty = H(STREAM_H_DIRTY) != 0;
+            rs.k_v = la[lane]; rs.cap_v = la[64 + lane]; rs.b_v = la[128 + lane];
+            rs.slot_v = la[192 + lane]; rs.dense_v = la[256 + lane];
+            const uint32_t rows = stream_lattice_words(rs.n) / 64;
+            if (rs.in_mem) {
+#pragma unroll
+                for (int k = 0; k < T0_RMEM; ++k) m.W[k * 64 + lane] = (uint32_t)k < rows ? lat[k * 64 + lane] : 0u;
+#pragma unroll
+                for (int k = 0; k < T0_RSMALL; ++k) W[k] = 0u;
+            } else {
+#pragma unroll
+                for (int k = 0; k < T0_RSMALL; ++k) W[k] = (uint32_t)k < rows ? lat[k * 64 + lane] : 0u;
+            }
+        } else {  // a fresh record: the model's initial state, nothing pending
+#pragma unroll
+            for (int k = 0; k < T0_RSMALL; ++k) W[k] = 0u;
+            if (lane == 0) W[0] = 1u << (a.init_state & 31u);
+            rs.dirty = true;
+        }
+        LatWalk lw;
+        lattice_walk<T0_RSMALL, true, false, EvSrc<true>, true>(W, lw, evp, nev, trp, it.ntr, 0u, m, ~0ull, false,
+                                                                false, &rs);
+        if (lw.status == 1) {
+            status = STREAM_INVALID;
+            fail = done + lw.fev;
+        } else if (lw.status) {  // more ops pending than the tier holds: the words lied about the key's width
+            status = STREAM_ERROR;
+            why = LC_BATCH_E_FIT;
+        } else {
+            la[lane] = rs.k_v; la[64 + lane] = rs.cap_v; la[128 + lane] = rs.b_v;
+            la[192 + lane] = rs.slot_v; la[256 + lane] = rs.dense_v;
+            const uint32_t rows = stream_lattice_words(rs.n) / 64;
+            if (rs.in_mem) {
+#pragma unroll
+                for (int k = 0; k < T0_RMEM; ++k)
+                    if ((uint32_t)k < rows) lat[k * 64 + lane] = m.W[k * 64 + lane];
+            } else {
+#pragma unroll
+                for (int k = 0; k < T0_RSMALL; ++k)
+                    if ((uint32_t)k < rows) lat[k * 64 + lane] = W[k];
+            }
+        }
+    }
+    uint32_t h = 0;
+    h = lane == STREAM_H_STATUS ? status : h;
+    h = lane == STREAM_H_N ? rs.n : h;
+    h = lane == STREAM_H_LIVE ? rs.live : h;
+    h = lane == STREAM_H_IN_MEM ? (uint32_t)rs.in_mem : h;
+    h = lane == STREAM_H_DIRTY ? (uint32_t)rs.dirty : h;
+    h = lane == STREAM_H_DONE ? (status == STREAM_LIVE ? done + nev : status == STREAM_INVALID ? fail : done) : h;
+    h = lane == STREAM_H_FAIL ? fail : h;
+    h = lane == STREAM_H_PEND0 ? pend[0] : h;
+    h = lane == STREAM_H_PEND1 ? pend[1] : h;
+    h = lane == STREAM_H_STARTED ? 1u : h;
+    if (lane < STREAM_HDR_WORDS) r[lane] = h;
+    if (status != STREAM_LIVE && lane == 0) {
+        const uint32_t i = atomicAdd(&a.out[0], 1u);
+        if (i < (uint32_t)a.n_items) {
+            uint32_t *o = a.out + 1 + 4 * (size_t)i;
+            o[0] = (uint32_t)it.key; o[1] = status; o[2] = fail; o[3] = (uint32_t)why;
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void k_stream(StreamArgs a) {
+    __shared__ uint32_t ws[3 * T0_RMEM * 64];  // lattices of 9-10 pending ops (12 KB)
+    for (int32_t w = blockIdx.x; w < a.n_items; w += gridDim.x) stream_key(a, w, ws);
+}
+
+hipError_t launch_stream(const StreamArgs &a, int grid, hipStream_t s) {
+    hipLaunchKernelGGL(k_stream, dim3(grid), dim3(64), 0, s, a);
     return hipGetLastError();
 }
 

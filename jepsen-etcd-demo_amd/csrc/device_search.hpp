@@ -99,6 +99,30 @@ size_t lat_ws_words();
 // tiers read the err words first and do nothing over a malformed batch)
 hipError_t launch_validate(const Args &a, hipStream_t s, bool general);
 
+// A resident search (lc_stream_*, device_lattice.hip k_stream): one wave per
+// work item resumes a key's register-tier walk from its state record
+// (stream_plan.hpp), searches the item's new event words and stores the
+// record back.  All arrays are device pointers.
+struct StreamItem {
+    int32_t key;           // the key's record
+    uint32_t ev_b, ev_e;   // its new words, events16[ev_b .. ev_e)
+    uint32_t tr_b, ntr;    // its transitions, trans[tr_b .. tr_b + ntr)
+    uint32_t ns;           // state ids it uses
+};
+struct StreamArgs {
+    const StreamItem *items;
+    const uint16_t *events16;
+    const uint32_t *trans;
+    uint32_t *rec;         // STREAM_REC_WORDS per key
+    // out[0] = keys that died in this launch (zeroed before it), then 4 words
+    // per such key: key, STREAM_INVALID / STREAM_ERROR, the failing event's
+    // ordinal in the key's stream, LC_BATCH_E_* bits
+    uint32_t *out;
+    int32_t n_items;
+    uint32_t init_state;
+};
+hipError_t launch_stream(const StreamArgs &a, int grid, hipStream_t s);
+
 // Key segments (device_lattice.hip, "Key segments"): a register-tier step
 // whose keys are cut at quiescent points and searched as independent
 // segments, then composed per key.  Device arrays of seg_cap entries each

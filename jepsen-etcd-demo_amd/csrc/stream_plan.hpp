@@ -1,0 +1,83 @@
+// A resident, resumable register-tier search (lc_stream_*):
+// the per-key state record k_stream (device_lattice.hip) loads and stores,
+// which of its words a load or a save touches, the phase a resumed walk
+// enters, and when a key leaves the stream for the batch path -- as pure
+// functions of plain values, tested without a GPU (tests/test_stream_plan.py).
+// No HIP here.
+//
+// A record is lattice_walk's state between two events of a key: the ops
+// pending (their transfers and window slots, one lane per op index), the
+// lattice W[L] over the subsets of those ops, and the two words of the slot
+// protocol (validate_chunk) carried from chunk to chunk.
+#pragma once
+
+#include <cstdint>
+
+namespace lc {
+
+// ---- record layout, in 32-bit words -------------------------------------------
+constexpr uint32_t STREAM_HDR_WORDS = 16;
+// header words
+constexpr uint32_t STREAM_H_STATUS = 0;   // STREAM_LIVE / _INVALID / _ERROR
+constexpr uint32_t STREAM_H_N = 1;        // ops pending
+constexpr uint32_t STREAM_H_LIVE = 2;     // occupied op indices
+constexpr uint32_t STREAM_H_IN_MEM = 3;   // the lattice is wider than the compact build's 4 registers
+constexpr uint32_t STREAM_H_DIRTY = 4;    // an op was invoked since the lattice was last closed
+constexpr uint32_t STREAM_H_DONE = 5;     // events searched so far
+constexpr uint32_t STREAM_H_FAIL = 6;     // STREAM_INVALID: ordinal of the failing :ok in the key's stream
+constexpr uint32_t STREAM_H_PEND0 = 7;    // window slots 0..31 pending (the slot protocol)
+constexpr uint32_t STREAM_H_PEND1 = 8;    // window slots 32..63
+constexpr uint32_t STREAM_H_STARTED = 9;  // 0: a fresh (zero-filled) record, the walk starts from the initial state
+// per-op lane arrays of the walk, 64 lanes each, in this order
+constexpr uint32_t STREAM_LANE_ARRAYS = 5;  // k_v, cap_v, b_v, slot_v, dense_v
+constexpr uint32_t STREAM_OFF_LANES = STREAM_HDR_WORDS;
+constexpr uint32_t STREAM_OFF_LATTICE = STREAM_OFF_LANES + STREAM_LANE_ARRAYS * 64;
+constexpr uint32_t STREAM_LATTICE_MAX = 1024;  // 10 ops pending: 16 registers x 64 lanes
+constexpr uint32_t STREAM_REC_WORDS = STREAM_OFF_LATTICE + STREAM_LATTICE_MAX;
+
+constexpr uint32_t STREAM_LIVE = 0, STREAM_INVALID = 1, STREAM_ERROR = 2;
+
+// the register tier's reach (device_lattice.hip T0_MAX_WIDTH / T0_MAX_STATES)
+constexpr uint32_t STREAM_MAX_WIDTH = 10;
+constexpr uint32_t STREAM_MAX_STATES = 32;
+// the least budget at which the FAST walk's sets are exact: no lattice holds
+// more than 16 registers x 64 lanes x 32 states
+constexpr uint64_t STREAM_MIN_BUDGET = 16ull * 64 * 32;
+
+// Lattice words of a key with n ops pending: one register (64 lanes) up to 6,
+// doubling with every op beyond; word k * 64 + lane = register k of the lane.
+constexpr uint32_t stream_lattice_words(uint32_t n) { return 64u << (n > 6 ? (n > 10 ? 4 : n - 6) : 0); }
+
+// Words a wave reads when it loads a record whose header says n ops pending
+// (the header is read first, then the lane arrays and the lattice rows in
+// use), and the words it writes when it stores one.  A key that died in this
+// call stores its header alone: its set is no longer followed.
+constexpr uint32_t stream_load_words(uint32_t n, bool started) {
+    return STREAM_HDR_WORDS + (started ? STREAM_LANE_ARRAYS * 64 + stream_lattice_words(n) : 0);
+}
+constexpr uint32_t stream_save_words(uint32_t n, bool dead) {
+    return STREAM_HDR_WORDS + (dead ? 0 : STREAM_LANE_ARRAYS * 64 + stream_lattice_words(n));
+}
+
+// The phase of lattice_walk a resume enters: the lane phase (0) with at most
+// 6 ops pending -- a 7th invoke then moves it to the dense phase as in an
+// unbroken walk -- and the dense phase (1) from 7 up, where op indices are
+// dense and the lattice is in registers 0..3 (7, 8) or the workspace (9, 10).
+constexpr int stream_resume_phase(uint32_t n) { return n >= 7 ? 1 : 0; }
+constexpr bool stream_in_workspace(uint32_t n) { return n >= 9; }
+
+// Deferral: an invoke that would take window slot `slot` or intern the key's
+// `states`-th state (nil included) ends the key's time on the device; from
+// that event on its words stay on the host and lc_stream_finish checks the
+// key once through the batch path.
+constexpr bool stream_defers(uint32_t slot, uint32_t states) {
+    return slot >= STREAM_MAX_WIDTH || states > STREAM_MAX_STATES;
+}
+
+// A register-tier key's descriptors at most: the read of anything, reads,
+// writes and cas pairs over 32 states (the streaming packer interns every
+// value an op names, so none carries LC_STATE_NONE) -- all below the 2,048 of
+// a 16-bit event word.
+constexpr uint32_t STREAM_MAX_DESC = 1 + 32 + 32 + 32 * 32;
+
+}  // namespace lc

@@ -165,6 +165,15 @@ class LcPerfResult(C.Structure):
                 ("rate_first", C.c_int64), ("rate_n", C.c_int64), ("q_first", C.c_int64), ("q_n", C.c_int64)]
 
 
+# ---- incremental check (lc_stream_*) -------------------------------------------
+LC_STREAM_REC_WORDS = 1360
+
+
+class LcStreamUpdate(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("events", C.c_int64), ("rows_held", C.c_int64), ("n_deferred", C.c_int64),
+                ("n_invalid", C.c_int64), ("invalid", P(C.c_int64))]
+
+
 # Every exported symbol: name -> (restype, argtypes).  tests/test_abi.py checks
 # this table against include/lincheck.h.
 SIGNATURES = {
@@ -244,6 +253,21 @@ SIGNATURES = {
     "lc_perf_hist_view": (C.c_int, [C.c_void_p, P(LcPerfHistory)]),
     "lc_perf_hist_name": (C.c_char_p, [C.c_void_p, C.c_int64]),
     "lc_perf_hist_free": (None, [C.c_void_p]),
+    "lc_stream_open": (C.c_int, [C.c_void_p, P(LcPackOpts), P(C.c_void_p)]),
+    "lc_stream_append": (C.c_int, [C.c_void_p, P(LcHistory), P(LcStreamUpdate)]),
+    "lc_stream_push": (C.c_int, [C.c_void_p, P(LcBatch), P(C.c_int64), P(LcStreamUpdate)]),
+    "lc_stream_finish": (C.c_int, [C.c_void_p, P(LcStreamUpdate)]),
+    "lc_stream_results": (C.c_int, [C.c_void_p, P(LcResult)]),
+    "lc_stream_keys": (C.c_int64, [C.c_void_p, P(C.c_int64)]),
+    "lc_stream_key_events": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_int64)]),
+    "lc_stream_event_row": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64]),
+    "lc_stream_key_words": (C.c_int64, [C.c_void_p, C.c_int64, P(C.c_uint32), C.c_int64]),
+    "lc_stream_key_trans": (C.c_int64, [C.c_void_p, C.c_int64, P(C.c_uint32), C.c_int64]),
+    "lc_stream_state_value": (C.c_int, [C.c_void_p, C.c_int64, C.c_uint32, P(C.c_int64), P(C.c_int)]),
+    "lc_stream_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_stream_record": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_uint32)]),
+    "lc_stream_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_stream_close": (None, [C.c_void_p]),
 }
 
 _lib: Optional[C.CDLL] = None

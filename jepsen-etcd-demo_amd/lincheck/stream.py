@@ -1,0 +1,172 @@
+"""Incremental check: a search that stays on the device while the history grows
+(lc_stream_*, include/lincheck.h).
+
+    s = Stream(dev)                  # or checker.linearizable(opts).stream(dev)
+    for rows in pieces_of_the_history:
+        up = s.append(rows)          # History columns, or a list of op maps
+        if up.invalid:               # keys whose decided prefix is not linearizable
+            stop_the_test()
+    s.finish()
+    res = s.results()                # valid / cause / fail_event per key
+
+Each call searches only the events that are new; a key's verdict after
+`finish` equals `Packed` + `Device.check` on the whole history.  A stream
+returns verdicts and failing events only, no final configs: to render the
+counterexample of a key found invalid, run the ordinary checker
+(`checker.linearizable(...).check`) on that key's sub-history.
+`failing_row(i)` names the history row of the :ok that could not be linearized.
+
+Models: cas-register, register and mutex.  (model/multi-register) and
+:algorithm :wgl have no register-tier search to resume and raise.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+
+from . import _native as N
+from .history import History
+from .model import CASRegister, MultiRegister
+
+
+class Update:
+    """What one call changed (lc_stream_update)."""
+
+    def __init__(self, u: N.LcStreamUpdate):
+        self.n_keys = int(u.n_keys)
+        self.events = int(u.events)
+        self.rows_held = int(u.rows_held)
+        self.n_deferred = int(u.n_deferred)
+        self.invalid = [int(u.invalid[i]) for i in range(int(u.n_invalid))]  # key indices, ascending
+
+    def __repr__(self):
+        return (f"Update(n_keys={self.n_keys}, events={self.events}, rows_held={self.rows_held}, "
+                f"n_deferred={self.n_deferred}, invalid={self.invalid})")
+
+
+class StreamResults:
+    def __init__(self, keys, valid, fail_event, cause):
+        self.keys, self.valid, self.fail_event, self.cause = keys, valid, fail_event, cause
+
+
+class Stream:
+    """A resident search on `dev` (a checker.Device), or a packer-only stream
+    (dev None: no device is needed, only the accessors work)."""
+
+    def __init__(self, dev=None, model=None):
+        self.model = model if model is not None else CASRegister()
+        if isinstance(self.model, MultiRegister):
+            raise NotImplementedError("a stream checks (model/cas-register), (model/register) and (model/mutex)")
+        self.dev = dev  # keeps the context alive
+        opts = N.LcPackOpts(self.model.code)
+        h = C.c_void_p()
+        N.check(N.lib().lc_stream_open(dev.handle if dev is not None else None, C.byref(opts), C.byref(h)))
+        self.handle = h
+
+    def close(self):
+        h = getattr(self, "handle", None)
+        if h:
+            N.lib().lc_stream_close(h)
+            self.handle = None
+
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    # -- feeding ------------------------------------------------------------
+    def append(self, rows) -> Update:
+        """History rows in history order: a History, or a list of op maps."""
+        hist = rows if isinstance(rows, History) else History.from_ops(rows)
+        c = hist.as_c()
+        u = N.LcStreamUpdate()
+        N.check(N.lib().lc_stream_append(self.handle, C.byref(c), C.byref(u)))
+        return Update(u)
+
+    def push(self, chunk: N.LcBatch, key_ids: Sequence[int]) -> Update:
+        """A caller-packed chunk (events mode): chunk key k continues stream
+        key key_ids[k].  Raises LincheckError (invalid) naming a key whose
+        words are malformed; the other keys have advanced."""
+        ids = np.ascontiguousarray(key_ids, dtype=np.int64)
+        if len(ids) != int(chunk.n_keys):
+            raise ValueError("one key id per chunk key")
+        u = N.LcStreamUpdate()
+        N.check(N.lib().lc_stream_push(self.handle, C.byref(chunk), N.ptr(ids if len(ids) else np.zeros(1, np.int64),
+                                                                          C.c_int64), C.byref(u)))
+        return Update(u)
+
+    def finish(self) -> Update:
+        u = N.LcStreamUpdate()
+        N.check(N.lib().lc_stream_finish(self.handle, C.byref(u)))
+        return Update(u)
+
+    # -- reading ------------------------------------------------------------
+    @property
+    def keys(self) -> list:
+        n = int(N.check(N.lib().lc_stream_keys(self.handle, None)))
+        out = np.zeros(max(n, 1), np.int64)
+        N.check(N.lib().lc_stream_keys(self.handle, N.ptr(out, C.c_int64)))
+        return [int(k) for k in out[:n]]
+
+    def results(self) -> StreamResults:
+        keys = self.keys
+        n = max(len(keys), 1)
+        valid, fev, cause = np.zeros(n, np.int8), np.zeros(n, np.int32), np.zeros(n, np.uint8)
+        r = N.LcResult()
+        r.valid, r.fail_event, r.cause = N.ptr(valid, C.c_int8), N.ptr(fev, C.c_int32), N.ptr(cause, C.c_uint8)
+        N.check(N.lib().lc_stream_results(self.handle, C.byref(r)))
+        k = len(keys)
+        return StreamResults(keys, valid[:k], fev[:k], cause[:k])
+
+    def key_events(self, i: int) -> dict:
+        out = np.zeros(4, np.int64)
+        N.check(N.lib().lc_stream_key_events(self.handle, i, N.ptr(out, C.c_int64)))
+        return {"emitted": int(out[0]), "held": int(out[1]), "deferred_at": int(out[2]), "searched": int(out[3])}
+
+    def event_row(self, i: int, j: int) -> int:
+        return int(N.check(N.lib().lc_stream_event_row(self.handle, i, j)))
+
+    def failing_row(self, i: int) -> Optional[int]:
+        """History row of the :ok key i could not linearize (rows mode), or None."""
+        res = self.results()
+        if res.valid[i] != N.LC_INVALID or res.fail_event[i] < 0:
+            return None
+        return self.event_row(i, int(res.fail_event[i]))
+
+    def words(self, i: int) -> np.ndarray:
+        n = int(N.check(N.lib().lc_stream_key_words(self.handle, i, None, 0)))
+        out = np.zeros(max(n, 1), np.uint32)
+        N.check(N.lib().lc_stream_key_words(self.handle, i, N.ptr(out, C.c_uint32), n))
+        return out[:n]
+
+    def trans(self, i: int) -> np.ndarray:
+        n = int(N.check(N.lib().lc_stream_key_trans(self.handle, i, None, 0)))
+        out = np.zeros(max(n, 1), np.uint32)
+        N.check(N.lib().lc_stream_key_trans(self.handle, i, N.ptr(out, C.c_uint32), n))
+        return out[:n]
+
+    def state_value(self, i: int, s: int):
+        v = C.c_int64(); nil = C.c_int()
+        N.check(N.lib().lc_stream_state_value(self.handle, i, s, C.byref(v), C.byref(nil)))
+        return None if nil.value else int(v.value)
+
+    def key_error(self, i: int) -> Optional[str]:
+        msg = N.lib().lc_stream_key_error(self.handle, i)
+        return None if msg is None else msg.decode(errors="replace")
+
+    def record(self, i: int) -> np.ndarray:
+        """Key i's device record (diagnostics; layout: csrc/stream_plan.hpp)."""
+        out = np.zeros(N.LC_STREAM_REC_WORDS, np.uint32)
+        N.check(N.lib().lc_stream_record(self.handle, i, N.ptr(out, C.c_uint32)))
+        return out
+
+    def last_timing(self) -> dict:
+        out = np.zeros(4, np.float64)
+        N.check(N.lib().lc_stream_last_timing(self.handle, N.ptr(out, C.c_double)))
+        return dict(zip(("pack_ms", "upload_ms", "kernel_ms", "readback_ms"), map(float, out)))

@@ -1,0 +1,240 @@
+#!/usr/bin/env python3
+"""Timing of the incremental check (lincheck.stream.Stream) on one MI355X.
+
+Shapes:
+  (a) the C1-shaped history, 100 rows per append: per-append latency
+  (b) C2's history merged round-robin (one row of each key in turn, 2 M rows),
+      in 20 and in 200 appends
+  (c) a C3-shard-sized history (12,500 keys x 2,000 ops), in 20 appends
+
+Per append: the host clock around the call, and the library's own split
+(lc_stream_last_timing): host packing, then device events around the upload,
+k_stream and the readback.  State bytes read and written are computed from
+the plan rule (csrc/stream_plan.hpp: header, five lane arrays, 64 x
+2^max(n - 6, 0) lattice words for n ops pending) and each key's pending count
+at the append's two ends.
+
+At (b) two comparisons, each form run --reps times alternating in this one
+process, after a warm-up round, records checked equal:
+  one-shot      lc_pack + lc_check_batch of the whole history, against the sum
+                of the appends: the price of resumability
+  from-scratch  what a caller had to do before: pack and check rows[0:r_i]
+                again at each of the 20 points
+
+--profile runs rocprofv3 --kernel-trace --stats in a run of its own (this
+script as the child, shape b, 20 appends, once) and reports k_stream's row.
+
+Writes one JSON document to --out (profiles/stream_timing.json).  Needs a GPU:
+there is no CPU path to time.
+"""
+import argparse
+import csv
+import glob
+import json
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "jepsen-etcd-demo_amd"))
+
+HDR, LANES = 16, 5 * 64  # stream_plan.hpp
+
+
+def lattice_words(n):
+    return 64 << max(min(n, 10) - 6, 0)
+
+
+def rows(h, lo, hi):
+    from lincheck import history as H
+    return H.History(h.type[lo:hi], h.f[lo:hi], h.process[lo:hi], h.key[lo:hi], h.v0[lo:hi], h.v1[lo:hi], h.index[lo:hi])
+
+
+def merged_round_robin(h):
+    """A key-major history's rows, one row of each key in turn."""
+    import numpy as np
+    from lincheck import history as H
+    key = h.key
+    start = np.flatnonzero(np.concatenate([[True], key[1:] != key[:-1]]))
+    block = np.repeat(np.arange(len(start)), np.diff(np.concatenate([start, [len(key)]])))
+    rank = np.arange(len(key)) - start[block]
+    perm = np.lexsort((block, rank))
+    return H.History(h.type[perm], h.f[perm], h.process[perm], h.key[perm], h.v0[perm], h.v1[perm],
+                     np.arange(len(perm), dtype=np.int64))
+
+
+def summary(xs):
+    xs = list(xs)
+    return {"median": statistics.median(xs), "min": min(xs), "max": max(xs), "n": len(xs)} if xs else None
+
+
+def state_bytes(s, searched_after):
+    """Record bytes read and written per append, from the plan rule."""
+    import numpy as np
+    n_app = len(searched_after)
+    rd, wr = [0] * n_app, [0] * n_app
+    K = len(searched_after[-1])
+    for i in range(K):
+        w = s.words(i)
+        pend = np.concatenate([[0], np.cumsum(np.where((w >> 31).astype(bool), -1, 1))])
+        prev = 0
+        for a in range(n_app):
+            cur = searched_after[a][i] if i < len(searched_after[a]) else 0
+            if cur > prev:
+                rd[a] += 4 * (HDR + (LANES + lattice_words(int(pend[prev])) if prev else 0))
+                wr[a] += 4 * (HDR + LANES + lattice_words(int(pend[cur])))
+            prev = cur
+    return rd, wr
+
+
+def run_stream(dev, h, n_appends, want=None, bytes_too=False):
+    import numpy as np
+    from lincheck.stream import Stream
+    n = len(h)
+    step = -(-n // n_appends)
+    s = Stream(dev)
+    per, searched = [], []
+    for lo in range(0, n, step):
+        part = rows(h, lo, min(n, lo + step))
+        t0 = time.perf_counter()
+        up = s.append(part)
+        wall = (time.perf_counter() - t0) * 1e3
+        t = s.last_timing()
+        per.append(dict(wall_ms=wall, events=up.events, rows_held=up.rows_held, **t))
+        if bytes_too:
+            searched.append([s.key_events(i)["searched"] for i in range(up.n_keys)])
+    t0 = time.perf_counter()
+    up = s.finish()
+    fin = (time.perf_counter() - t0) * 1e3
+    res = s.results()
+    if want is not None:
+        assert np.array_equal(res.valid, want.valid) and np.array_equal(res.fail_event, want.fail_event) and \
+            np.array_equal(res.cause, want.cause), "stream records differ from the one-shot check"
+    out = dict(appends=len(per), finish_ms=fin, n_deferred=up.n_deferred, total_ms=sum(p["wall_ms"] for p in per) + fin,
+               events=sum(p["events"] for p in per), per_append=per)
+    if bytes_too:
+        searched.append([s.key_events(i)["searched"] for i in range(len(res.keys))])
+        rd, wr = state_bytes(s, searched[:-1] if len(searched) > len(per) else searched)
+        out["state_bytes_read"], out["state_bytes_written"] = rd, wr
+    s.close()
+    return out
+
+
+def digest(run):
+    keys = ("wall_ms", "pack_ms", "upload_ms", "kernel_ms", "readback_ms")
+    d = {k: summary(p[k] for p in run["per_append"]) for k in keys}
+    d.update(appends=run["appends"], total_ms=run["total_ms"], finish_ms=run["finish_ms"], events=run["events"],
+             n_deferred=run["n_deferred"])
+    for k in ("state_bytes_read", "state_bytes_written"):
+        if k in run:
+            d[k] = summary(run[k])
+            d[k]["sum"] = sum(run[k])
+    return d
+
+
+def one_shot(dev, h):
+    from lincheck.checker import Packed
+    t0 = time.perf_counter()
+    pk = Packed(h)
+    t1 = time.perf_counter()
+    r = dev.check(pk, verdicts_only=True)
+    t2 = time.perf_counter()
+    return dict(pack_ms=(t1 - t0) * 1e3, check_ms=(t2 - t1) * 1e3, total_ms=(t2 - t0) * 1e3,
+                kernel_ms=r.stats["kernel_ms"]), r
+
+
+def shape_a(dev, reps):
+    from lincheck import history as H
+    h = H.synth(**H.CONFIGS["C1"])
+    _, want = one_shot(dev, h)
+    n_app = -(-len(h) // 100)
+    run_stream(dev, h, n_app, want)
+    runs = [run_stream(dev, h, n_app, want, bytes_too=(r == 0)) for r in range(reps)]
+    return dict(shape="a", rows=len(h), rows_per_append=100, runs=[digest(r) for r in runs])
+
+
+def shape_b(dev, reps, appends=(20, 200)):
+    from lincheck import history as H
+    h = merged_round_robin(H.synth(**H.CONFIGS["C2"]))
+    n = len(h)
+    points = [min(n, (i + 1) * -(-n // 20)) for i in range(20)]
+    _, want = one_shot(dev, h)
+    run_stream(dev, h, 20, want)  # warm-up of every form
+    out = dict(shape="b", rows=n, forms={f"stream_{a}": [] for a in appends})
+    out["forms"]["one_shot"], out["forms"]["from_scratch_20"] = [], []
+    for r in range(reps):  # the forms alternate
+        for a in appends:
+            out["forms"][f"stream_{a}"].append(digest(run_stream(dev, h, a, want, bytes_too=(r == 0))))
+        o, _ = one_shot(dev, h)
+        out["forms"]["one_shot"].append(o)
+        t0 = time.perf_counter()
+        ev = 0
+        for p in points:
+            o, res = one_shot(dev, rows(h, 0, p))
+            ev += int(res.stats["events"])
+        out["forms"]["from_scratch_20"].append(dict(total_ms=(time.perf_counter() - t0) * 1e3, points=len(points)))
+    tot = lambda f: summary(x["total_ms"] for x in out["forms"][f])
+    out["totals_ms"] = {f: tot(f) for f in out["forms"]}
+    return out
+
+
+def shape_c(dev, reps):
+    from lincheck import history as H
+    h = H.synth(n_keys=12_500, ops_per_key=2000, concurrency=10, seed=3)
+    _, want = one_shot(dev, h)
+    runs = [run_stream(dev, h, 20, want) for _ in range(max(1, reps - 1))]
+    return dict(shape="c", rows=len(h), runs=[digest(r) for r in runs])
+
+
+def profile():
+    """k_stream's row of rocprofv3 --kernel-trace --stats, in a run of its own."""
+    d = tempfile.mkdtemp(prefix="stream_prof_")
+    cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "kt", "--output-format", "csv", "--", sys.executable,
+           os.path.abspath(__file__), "--shapes", "b", "--reps", "1", "--appends", "20", "--out", os.path.join(d, "child.json")]
+    subprocess.run(cmd, check=True, timeout=900, capture_output=True)
+    for path in glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            if "k_stream" in row.get("Name", ""):
+                return {k: row[k] for k in row if k in ("Name", "Calls", "TotalDurationNs", "AverageNs", "MinNs", "MaxNs")}
+    return None
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--shapes", default="a,b,c")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--appends", default="20,200", help="shape b: the append counts")
+    ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_timing.json"))
+    a = ap.parse_args()
+    from lincheck import _native as N
+    from lincheck.checker import Device
+    if N.lib().lc_device_count() < 1:
+        sys.exit("stream_timing: no GPU visible; there is nothing to time without one")
+    dev = Device(0)
+    doc = {"shapes": []}
+    for sh in a.shapes.split(","):
+        if sh == "a":
+            doc["shapes"].append(shape_a(dev, a.reps))
+        elif sh == "b":
+            doc["shapes"].append(shape_b(dev, a.reps, tuple(int(x) for x in a.appends.split(","))))
+        elif sh == "c":
+            doc["shapes"].append(shape_c(dev, a.reps))
+        print(json.dumps({k: v for k, v in doc["shapes"][-1].items() if k != "forms"})[:2000], flush=True)
+    if a.profile:
+        try:
+            doc["k_stream_rocprofv3"] = profile()
+        except (OSError, subprocess.SubprocessError) as e:
+            doc["k_stream_rocprofv3"] = {"error": repr(e)[:300]}
+        print(json.dumps(doc["k_stream_rocprofv3"]), flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(doc, f, indent=1)
+    print("wrote", a.out)
+
+
+if __name__ == "__main__":
+    main()
