@@ -926,6 +926,15 @@ void lc_perf_hist_free(lc_perf_hist *h);
  * whose next invoke would pass either is DEFERRED: from that event on its
  * words stay on the host, and lc_stream_finish checks the key once, from its
  * first event, through lc_check_batch with the context's budget.
+ *   With LC_STREAM_SET_TIER (lc_stream_open_opts; rows mode only) such a key is
+ * not restarted: it MIGRATES to a resident set tier on the device -- its
+ * search state written out as a config set of at most 32,768 configs -- and
+ * keeps being searched as rows arrive, so it too turns invalid in the call
+ * whose decided prefix holds its failing :ok.  A migrated key FALLS BACK to
+ * the deferral above when a set or a closure of it would pass 32,768 configs,
+ * an invoke takes window slot 56 or above, or the key names more than 255
+ * register values.  The guarantee after lc_stream_finish is unchanged: every
+ * key's valid, cause and fail_event equal the one-shot check's.
  *
  * Events mode (lc_stream_push): the caller packs chunks itself.  Chunk key k
  * continues stream key key_ids[k] (new ids are new keys, in order of first
@@ -955,6 +964,20 @@ typedef struct lc_stream_update {
 
 #define LC_STREAM_REC_WORDS 1360  /* a key's device record, 32-bit words (csrc/stream_plan.hpp) */
 
+/* Options of a stream beyond the packer's (additive to ABI 13). */
+#define LC_STREAM_SET_TIER 1u     /* keys past the register tier resume in the resident set tier */
+typedef struct lc_stream_opts {
+    uint32_t flags;               /* LC_STREAM_* bits; 0: as lc_stream_open */
+} lc_stream_opts;
+
+/* Where a key of a stream is searched (lc_stream_key_tier). */
+#define LC_STREAM_TIER_REGISTER    0  /* the register tier's resident record                     */
+#define LC_STREAM_TIER_SET         1  /* the resident set tier                                   */
+#define LC_STREAM_TIER_FALLEN_BACK 2  /* deferred: lc_stream_finish checks it from its first event
+                                         (without LC_STREAM_SET_TIER: every deferred key)        */
+#define LC_STREAM_TIER_DEAD        3  /* invalid or in error: nothing more of it is searched     */
+#define LC_STREAM_SET_HEAD_WORDS 80   /* header (16) and descriptors (64) of a set record        */
+
 /* ctx NULL: a packer-only stream (rows mode without a device: the accessors
  * below work, lc_stream_results does not).  opts NULL: cas-register.  A
  * context of several devices or with a communicator, or one whose budget is
@@ -962,6 +985,11 @@ typedef struct lc_stream_update {
  * with LC_E_UNSUPPORTED; so is LC_MODEL_MULTI_REGISTER.  The context must
  * outlive the stream. */
 int  lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream **out);
+/* The same with stream options (sopts NULL: none).  LC_STREAM_SET_TIER on a
+ * packer-only stream and in events mode has no effect (lc_stream_push keeps
+ * refusing a key_width above 10); with it n_deferred counts the keys that
+ * fell back. */
+int  lc_stream_open_opts(lc_ctx *ctx, const lc_pack_opts *opts, const lc_stream_opts *sopts, lc_stream **out);
 int  lc_stream_append(lc_stream *s, const lc_history *rows, lc_stream_update *u);
 int  lc_stream_push(lc_stream *s, const lc_batch *chunk, const int64_t *key_ids, lc_stream_update *u);
 int  lc_stream_finish(lc_stream *s, lc_stream_update *u);
@@ -990,6 +1018,21 @@ const char *lc_stream_key_error(const lc_stream *s, int64_t i);
  * [3] readback (device events). */
 int  lc_stream_record(lc_stream *s, int64_t i, uint32_t *out);
 int  lc_stream_last_timing(const lc_stream *s, double *out_ms4);
+/* Key i's tier (LC_STREAM_TIER_*; negative: an error code), and the count of
+ * keys in each, out4[tier].  deferred_at (lc_stream_key_events) names the
+ * event at which a key left the register tier, whatever became of it. */
+int  lc_stream_key_tier(const lc_stream *s, int64_t i);
+int  lc_stream_tiers(const lc_stream *s, int64_t *out4);
+/* Diagnostics of the set tier.  lc_stream_set_record: key i's set record as
+ * it is in device memory (csrc/stream_plan.hpp) -- LC_STREAM_SET_HEAD_WORDS
+ * words of header and descriptors, then the current set's configs, two words
+ * each (low, high; state << 56 | window-slot bits); returns the word count
+ * and writes at most cap; LC_E_INVALID for a key that is not in the set tier.
+ * lc_stream_set_stats: out6 = device ms of the last call's migrations and of
+ * its k_stream_set launch; the set-record pool's slots allocated, in use, most
+ * in use at once, and bytes per slot. */
+int64_t lc_stream_set_record(lc_stream *s, int64_t i, uint32_t *out, int64_t cap);
+int  lc_stream_set_stats(const lc_stream *s, double *out6);
 void lc_stream_close(lc_stream *s);
 
 #ifdef __cplusplus

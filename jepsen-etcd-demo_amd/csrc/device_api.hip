@@ -2525,13 +2525,47 @@ struct lcst::StreamDev {
     size_t in_cap = 0;
     uint32_t *dout = nullptr, *hout = nullptr;  // the dead list
     size_t out_cap = 0;        // words
-    hipEvent_t ev[4] = {};
+    hipEvent_t ev[6] = {};     // [4], [5]: after the migrations, after k_stream_set
     float ms[3] = {0, 0, 0};
+    // the resident set tier: the set-record pool -- chunk c holds
+    // SET_CHUNK0 << c slots of stream_set_slot_bytes() and never moves -- and
+    // k_stream_set's workspace, one slot per resident workgroup
+    std::vector<uint32_t *> set_chunk;
+    std::vector<int32_t> set_free;
+    int64_t set_slots = 0, set_used = 0, set_peak = 0;
+    char *set_ws = nullptr;
+    int set_ws_slots = 0;
+    float set_ms[2] = {0, 0};
 };
 
 namespace {
 constexpr size_t STREAM_OUT_HEAD = 63;  // dead keys read back with the count, in one copy
+constexpr int64_t SET_CHUNK0 = 4;       // slots of the set-record pool's first chunk
+constexpr int SET_GRID = 64;            // k_stream_set workgroups (and workspace slots) at most
 size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
+
+// Pool slot -> its record (chunk c starts at slot SET_CHUNK0 * (2^c - 1)).
+uint32_t *set_slot_ptr(const lcst::StreamDev *s, int64_t slot) {
+    if (slot < 0 || slot >= s->set_slots) return nullptr;
+    int c = 0;
+    int64_t first = 0;
+    while (slot >= first + (SET_CHUNK0 << c)) first += SET_CHUNK0 << c++;
+    return s->set_chunk[(size_t)c] + (size_t)(slot - first) * lc::STREAM_SET_REC_WORDS;
+}
+
+// k_stream_set's workspace for `slots` resident workgroups, hash sets empty.
+int set_ws_grow(lcst::StreamDev *s, Dev *d, int slots) {
+    if (slots <= s->set_ws_slots) return LC_OK;
+    const lcd::StreamSetWs w = lcd::stream_set_ws_layout();
+    const int want = std::min(SET_GRID, std::max(slots, 2 * s->set_ws_slots));
+    if (s->set_ws) (void)hipFree(s->set_ws);
+    s->set_ws = nullptr;
+    s->set_ws_slots = 0;
+    HIPCHK(hipMalloc((void **)&s->set_ws, (size_t)want * w.slot_bytes));
+    HIPCHK(hipMemsetAsync(s->set_ws, 0xFF, (size_t)want * w.slot_bytes, d->stream));  // EMPTY tables
+    s->set_ws_slots = want;
+    return LC_OK;
+}
 
 int stream_grow(lcst::StreamDev *s, Dev *d, int64_t n_keys, size_t in_bytes, size_t out_words) {
     if (n_keys > s->rec_cap) {
@@ -2606,6 +2640,8 @@ void lcst::stream_dev_close(StreamDev *s) {
     (void)hipStreamSynchronize(d->stream);
     dfree(s->rec);
     dfree(s->dout);
+    for (uint32_t *&c : s->set_chunk) dfree(c);
+    if (s->set_ws) (void)hipFree(s->set_ws);
     if (s->din) (void)hipFree(s->din);
     if (s->hin) (void)hipHostFree(s->hin);
     if (s->hout) (void)hipHostFree(s->hout);
@@ -2616,6 +2652,54 @@ void lcst::stream_dev_close(StreamDev *s) {
 
 void lcst::stream_dev_timing(const StreamDev *s, double *out3) {
     for (int i = 0; i < 3; ++i) out3[i] = s->ms[i];
+}
+
+int lcst::stream_dev_set_alloc(StreamDev *s, int32_t *slot) {
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    if (s->set_free.empty()) {
+        if (s->set_slots > ((int64_t)1 << 20)) return lc::fail(LC_E_DEVICE, "lc_stream: the set-record pool is full");
+        HIPCHK(hipSetDevice(s->ctx->dev[0]->device));
+        const int64_t n = SET_CHUNK0 << s->set_chunk.size();
+        uint32_t *c = nullptr;
+        HIPCHK(dalloc(&c, (size_t)n * lc::STREAM_SET_REC_WORDS));
+        s->set_chunk.push_back(c);
+        for (int64_t i = n; i-- > 0;) s->set_free.push_back((int32_t)(s->set_slots + i));
+        s->set_slots += n;
+    }
+    *slot = s->set_free.back();
+    s->set_free.pop_back();
+    s->set_peak = std::max(s->set_peak, ++s->set_used);
+    return LC_OK;
+}
+
+void lcst::stream_dev_set_free(StreamDev *s, int32_t slot) {
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    if (slot < 0 || slot >= s->set_slots) return;
+    s->set_free.push_back(slot);
+    --s->set_used;
+}
+
+void lcst::stream_dev_set_stats(const StreamDev *s, double *out6) {
+    out6[0] = s->set_ms[0];
+    out6[1] = s->set_ms[1];
+    out6[2] = (double)s->set_slots;
+    out6[3] = (double)s->set_used;
+    out6[4] = (double)s->set_peak;
+    out6[5] = (double)lc::stream_set_slot_bytes();
+}
+
+int lcst::stream_dev_set_record(StreamDev *s, int32_t slot, int64_t off, uint32_t *out, int64_t words) {
+    std::lock_guard<std::mutex> g(s->ctx->mu);
+    const uint32_t *p = set_slot_ptr(s, slot);
+    if (!p || off < 0 || words < 0 || off + words > (int64_t)lc::STREAM_SET_REC_WORDS)
+        return lc::fail(LC_E_INVALID, "lc_stream_set_record: no such record");
+    if (!words) return LC_OK;
+    Dev *d = s->ctx->dev[0];
+    HIPCHK(hipSetDevice(d->device));
+    LCCHK(join_lanes(d));
+    HIPCHK(hipMemcpyAsync(out, p + off, (size_t)words * 4, hipMemcpyDeviceToHost, d->stream));
+    HIPCHK(hipStreamSynchronize(d->stream));
+    return LC_OK;
 }
 
 int lcst::stream_dev_record(StreamDev *s, int64_t key, uint32_t *out) {
@@ -2632,12 +2716,28 @@ int lcst::stream_dev_record(StreamDev *s, int64_t key, uint32_t *out) {
 
 int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
                           uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
-                          std::vector<Dead> *dead) {
+                          std::vector<Dead> *dead, const SetWork *set) {
     dead->clear();
     s->ms[0] = s->ms[1] = s->ms[2] = 0;
-    if (n_items <= 0) return LC_OK;
-    if (n_items > (int64_t)1 << 30 || n_ev > 0xFFFFFFFFull || n_trans > 0xFFFFFFFFull)
+    s->set_ms[0] = s->set_ms[1] = 0;
+    const int64_t n_mig = set ? set->n_mig : 0, n_set = set ? set->n_items : 0;
+    const uint64_t n_ev32 = set ? set->n_ev32 : 0;
+    if (n_items <= 0 && n_mig <= 0 && n_set <= 0) return LC_OK;
+    if (n_items < 0) n_items = 0;
+    if (n_items > (int64_t)1 << 30 || n_ev > 0xFFFFFFFFull || n_trans > 0xFFFFFFFFull || n_mig > (int64_t)1 << 24 ||
+        n_set > (int64_t)1 << 24 || n_ev32 > 0x3FFFFFFFull)
         return lc::fail(LC_E_INVALID, "lc_stream: too much for one call");
+    for (int64_t i = 0; i < n_mig; ++i) {
+        const SetMig &m = set->mig[i];
+        if (m.key < 0 || m.key >= n_keys || !set_slot_ptr(s, m.slot))
+            return lc::fail(LC_E_INVALID, "lc_stream: migration %lld is out of range (internal error)", (long long)i);
+    }
+    for (int64_t i = 0; i < n_set; ++i) {
+        const SetItem &it = set->items[i];
+        if (it.key < 0 || it.key >= n_keys || !set_slot_ptr(s, it.slot) || it.ev_b > it.ev_e || it.ev_e > n_ev32 ||
+            it.tr_b > n_trans || it.ntr > n_trans - it.tr_b)
+            return lc::fail(LC_E_INVALID, "lc_stream: set work item %lld is out of range (internal error)", (long long)i);
+    }
     // every index a wave follows, checked before the launch
     for (int64_t i = 0; i < n_items; ++i) {
         const Item &it = items[i];
@@ -2650,16 +2750,35 @@ int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64
     Dev *d = c->dev[0];
     HIPCHK(hipSetDevice(d->device));
     LCCHK(join_lanes(d));
+    const bool sets = n_mig > 0 || n_set > 0;
     const size_t o_items = 0, o_trans = up16((size_t)n_items * sizeof(Item)),
-                 o_ev = o_trans + up16((size_t)n_trans * 4), in_bytes = o_ev + up16((size_t)n_ev * 2);
-    const size_t out_words = 1 + 4 * (size_t)n_items;
+                 o_ev = o_trans + up16((size_t)n_trans * 4), o_mig = o_ev + up16((size_t)n_ev * 2),
+                 o_desc = o_mig + up16((size_t)n_mig * sizeof(lcd::StreamMigItem)),
+                 o_set = o_desc + up16((size_t)n_mig * 64 * 4),
+                 o_ev32 = o_set + up16((size_t)n_set * sizeof(lcd::StreamSetItem)),
+                 in_bytes = o_ev32 + up16((size_t)n_ev32 * 4);
+    // the set tier's list follows k_stream's
+    const size_t o_out2 = 1 + 4 * (size_t)n_items, out_words = o_out2 + (sets ? 1 + 4 * (size_t)n_set : 0);
     LCCHK(stream_grow(s, d, n_keys, in_bytes, out_words));
-    std::memcpy(s->hin + o_items, items, (size_t)n_items * sizeof(Item));
+    if (n_set) LCCHK(set_ws_grow(s, d, (int)std::min<int64_t>(n_set, SET_GRID)));
+    if (n_items) std::memcpy(s->hin + o_items, items, (size_t)n_items * sizeof(Item));
     if (n_trans) std::memcpy(s->hin + o_trans, trans, (size_t)n_trans * 4);
     if (n_ev) std::memcpy(s->hin + o_ev, ev16, (size_t)n_ev * 2);
+    for (int64_t i = 0; i < n_mig; ++i) {
+        lcd::StreamMigItem m{set_slot_ptr(s, set->mig[i].slot), set->mig[i].key, (uint32_t)i * 64u};
+        std::memcpy(s->hin + o_mig + (size_t)i * sizeof m, &m, sizeof m);
+        std::memcpy(s->hin + o_desc + (size_t)i * 64 * 4, set->mig[i].descs, 64 * 4);
+    }
+    for (int64_t i = 0; i < n_set; ++i) {
+        const SetItem &it = set->items[i];
+        lcd::StreamSetItem m{set_slot_ptr(s, it.slot), it.key, it.ev_b, it.ev_e, it.tr_b, it.ntr, 0u};
+        std::memcpy(s->hin + o_set + (size_t)i * sizeof m, &m, sizeof m);
+    }
+    if (n_ev32) std::memcpy(s->hin + o_ev32, set->ev32, (size_t)n_ev32 * 4);
     HIPCHK(hipEventRecord(s->ev[0], d->stream));
     HIPCHK(hipMemcpyAsync(s->din, s->hin, in_bytes, hipMemcpyHostToDevice, d->stream));
     HIPCHK(hipMemsetAsync(s->dout, 0, 4, d->stream));
+    if (sets) HIPCHK(hipMemsetAsync(s->dout + o_out2, 0, 4, d->stream));
     HIPCHK(hipEventRecord(s->ev[1], d->stream));
     lcd::StreamArgs a{};
     a.items = (const lcd::StreamItem *)(s->din + o_items);
@@ -2669,9 +2788,30 @@ int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64
     a.out = s->dout;
     a.n_items = (int32_t)n_items;
     a.init_state = init_state;
-    HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(n_items, 8192), d->stream));
+    if (n_items) HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(n_items, 8192), d->stream));
     HIPCHK(hipEventRecord(s->ev[2], d->stream));
-    const size_t head = std::min<size_t>(out_words, 1 + 4 * STREAM_OUT_HEAD);
+    if (sets) {
+        // in this order on the one lane: a key's register words, its migration,
+        // its set words -- each launch sees what the one before it stored
+        lcd::StreamSetArgs sa{};
+        sa.mig = (const lcd::StreamMigItem *)(s->din + o_mig);
+        sa.descs = (const uint32_t *)(s->din + o_desc);
+        sa.rec = s->rec;
+        sa.items = (const lcd::StreamSetItem *)(s->din + o_set);
+        sa.events32 = (const uint32_t *)(s->din + o_ev32);
+        sa.trans = a.trans;
+        sa.ws = lcd::stream_set_ws_layout();
+        sa.ws.base = s->set_ws;
+        sa.out = s->dout + o_out2;
+        sa.n_mig = (int32_t)n_mig;
+        sa.n_items = (int32_t)n_set;
+        sa.init_state = init_state;
+        if (n_mig) HIPCHK(lcd::launch_stream_migrate(sa, (int)std::min<int64_t>(n_mig, 8192), d->stream));
+        HIPCHK(hipEventRecord(s->ev[4], d->stream));
+        if (n_set) HIPCHK(lcd::launch_stream_set(sa, (int)std::min<int64_t>(n_set, s->set_ws_slots), d->stream));
+        HIPCHK(hipEventRecord(s->ev[5], d->stream));
+    }
+    const size_t head = sets ? out_words : std::min<size_t>(out_words, 1 + 4 * STREAM_OUT_HEAD);
     HIPCHK(hipMemcpyAsync(s->hout, s->dout, head * 4, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipEventRecord(s->ev[3], d->stream));
     HIPCHK(hipStreamSynchronize(d->stream));
@@ -2681,11 +2821,23 @@ int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64
         HIPCHK(hipMemcpyAsync(s->hout + head, s->dout + head, (1 + 4 * n_dead - head) * 4, hipMemcpyDeviceToHost, d->stream));
         HIPCHK(hipStreamSynchronize(d->stream));
     }
-    for (int i = 0; i < 3; ++i) (void)hipEventElapsedTime(&s->ms[i], s->ev[i], s->ev[i + 1]);
-    dead->resize(n_dead);
+    const size_t n_left = sets ? s->hout[o_out2] : 0;
+    if (n_left > (size_t)n_set) return lc::fail(LC_E_DEVICE, "lc_stream: the set tier's list holds more keys than the launch had");
+    (void)hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]);
+    (void)hipEventElapsedTime(&s->ms[1], s->ev[1], s->ev[2]);
+    (void)hipEventElapsedTime(&s->ms[2], s->ev[sets ? 5 : 2], s->ev[3]);
+    if (sets) {
+        (void)hipEventElapsedTime(&s->set_ms[0], s->ev[2], s->ev[4]);
+        (void)hipEventElapsedTime(&s->set_ms[1], s->ev[4], s->ev[5]);
+    }
+    dead->resize(n_dead + n_left);
     for (size_t i = 0; i < n_dead; ++i) {
         const uint32_t *o = s->hout + 1 + 4 * i;
         (*dead)[i] = Dead{o[0], o[1], o[2], o[3]};
+    }
+    for (size_t i = 0; i < n_left; ++i) {
+        const uint32_t *o = s->hout + o_out2 + 1 + 4 * i;
+        (*dead)[n_dead + i] = Dead{o[0], o[1], o[2], o[3]};
     }
     std::sort(dead->begin(), dead->end(), [](const Dead &x, const Dead &y) { return x.key < y.key; });
     return LC_OK;

@@ -123,6 +123,49 @@ struct StreamArgs {
 };
 hipError_t launch_stream(const StreamArgs &a, int grid, hipStream_t s);
 
+// The resident set tier of a stream (device_stream_set.hip; the set record's
+// layout: stream_plan.hpp).  A migration item turns a key's register record
+// into a set record; a set item searches the key's new 32-bit event words from
+// its set record.  All arrays are device pointers.
+struct StreamMigItem {
+    uint32_t *set_rec;     // the key's set record (a pool slot)
+    int32_t key;           // its register record
+    uint32_t desc_b;       // its pending ops' descriptors by window slot, descs[desc_b .. desc_b + 64)
+};
+struct StreamSetItem {
+    uint32_t *set_rec;
+    int32_t key;
+    uint32_t ev_b, ev_e;   // its new words, events32[ev_b .. ev_e)
+    uint32_t tr_b, ntr;    // its transitions, trans[tr_b .. tr_b + ntr)
+    uint32_t pad;
+};
+// Per-resident-block workspace of k_stream_set: the closure I, the two hash
+// sets and the table positions of the entries they hold.
+struct StreamSetWs {
+    char *base;
+    size_t slot_bytes;
+    uint32_t hmask;        // hash slots - 1 (each table)
+    size_t off_I, off_hS, off_hI, off_pS, off_pI;
+};
+StreamSetWs stream_set_ws_layout();
+struct StreamSetArgs {
+    const StreamMigItem *mig;
+    const uint32_t *descs;
+    const uint32_t *rec;   // the register records (STREAM_REC_WORDS per key)
+    const StreamSetItem *items;
+    const uint32_t *events32;
+    const uint32_t *trans;
+    StreamSetWs ws;
+    // out[0] = keys that left the set tier in this launch (zeroed before it),
+    // then 4 words per such key: key, STREAM_INVALID / STREAM_ERROR /
+    // STREAM_SET_FALLBACK, the event's ordinal in the key's stream, reason bits
+    uint32_t *out;
+    int32_t n_mig, n_items;
+    uint32_t init_state;
+};
+hipError_t launch_stream_migrate(const StreamSetArgs &a, int grid, hipStream_t s);
+hipError_t launch_stream_set(const StreamSetArgs &a, int grid, hipStream_t s);
+
 // Key segments (device_lattice.hip, "Key segments"): a register-tier step
 // whose keys are cut at quiescent points and searched as independent
 // segments, then composed per key.  Device arrays of seg_cap entries each

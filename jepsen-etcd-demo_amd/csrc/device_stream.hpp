@@ -25,6 +25,27 @@ struct Dead {
     uint32_t key, status, fail_event, why;  // STREAM_INVALID / STREAM_ERROR; LC_BATCH_E_* bits
 };
 
+// The resident set tier's work of a call (LC_STREAM_SET_TIER): keys that
+// migrate from their register record into pool slot `slot`, with their pending
+// ops' descriptors by window slot, and keys searched from their set record.
+struct SetMig {
+    int32_t key, slot;
+    uint32_t descs[64];
+};
+struct SetItem {
+    int32_t key, slot;
+    uint32_t ev_b, ev_e;  // its new 32-bit words
+    uint32_t tr_b, ntr;   // its transitions
+};
+struct SetWork {
+    const SetMig *mig;
+    int64_t n_mig;
+    const SetItem *items;
+    int64_t n_items;
+    const uint32_t *ev32;
+    uint64_t n_ev32;
+};
+
 // Refuses (LC_E_UNSUPPORTED) a context with several devices or a
 // communicator, or a budget below the FAST walk's exact range.
 int stream_dev_open(lc_ctx *c, StreamDev **out);
@@ -32,9 +53,21 @@ void stream_dev_close(StreamDev *d);
 // Search the items' words (one k_stream launch on the context's lane 0,
 // joined behind lane 1) and return the keys that died, ascending by key.
 // n_keys: the stream's keys so far (records are grown, zero-filled, to hold them).
+// set (may be null): after k_stream, on the same lane, the migrations and then
+// one k_stream_set launch; keys that left the set tier are in `dead` too
+// (status STREAM_SET_FALLBACK for those that fell back).
 int stream_dev_push(StreamDev *d, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
                     uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
-                    std::vector<Dead> *dead);
+                    std::vector<Dead> *dead, const SetWork *set = nullptr);
+// The set-record pool: a slot for a migrating key (the pool is allocated on
+// first use and grows geometrically, in chunks that never move), and its return.
+int stream_dev_set_alloc(StreamDev *d, int32_t *slot);
+void stream_dev_set_free(StreamDev *d, int32_t slot);
+// Words off .. off + words of pool slot `slot` as they are in device memory.
+int stream_dev_set_record(StreamDev *d, int32_t slot, int64_t off, uint32_t *out, int64_t words);
+// [0] migration, [1] k_stream_set device time of the last push, ms; the pool's
+// [2] slots allocated, [3] in use, [4] most in use at once, [5] bytes per slot.
+void stream_dev_set_stats(const StreamDev *d, double *out6);
 // Key's record as it is in device memory (STREAM_REC_WORDS words).
 int stream_dev_record(StreamDev *d, int64_t key, uint32_t *out);
 // Device-event times of the last push, ms: upload, k_stream, readback.

@@ -16,6 +16,13 @@
 // transition ids are per key and stable for the stream's life (nil = state 0);
 // every value an op names is interned when the op is emitted, reads included:
 // a read may precede the write that installs its value.
+//
+// With LC_STREAM_SET_TIER (lc_stream_open_opts) a key that leaves the register
+// tier is not held for lc_stream_finish: send_rows sends its words past
+// defer_at too -- the first time with a migration item (the key's pool slot and
+// its pending ops' descriptors by window slot), later to its set record
+// (device_stream_set.hip).  A key the set tier cannot hold falls back to the
+// deferral (stream_plan.hpp stream_set_falls_back) and its slot is reused.
 
 #include <algorithm>
 #include <chrono>
@@ -81,6 +88,9 @@ struct SKey {
     int32_t fail_event = -1;
     bool dead = false;               // invalid or in error on the device: no more words go there
     bool touched = false;
+    // ---- the resident set tier (LC_STREAM_SET_TIER)
+    int32_t set_slot = -1;           // its set record in the pool, while it is in the set tier
+    bool fell_back = false;          // it left the set tier (or could not enter it): checked at finish
 };
 
 }  // namespace
@@ -105,6 +115,10 @@ struct lc_stream {
     std::vector<uint16_t> ev16;
     std::vector<uint32_t> trans;
     std::vector<lcst::Dead> dead;
+    bool set_tier = false;  // LC_STREAM_SET_TIER, on a stream with a device
+    std::vector<lcst::SetMig> set_mig;
+    std::vector<lcst::SetItem> set_items;
+    std::vector<uint32_t> ev32;
 };
 
 namespace {
@@ -226,7 +240,7 @@ void drain(lc_stream *s, SKey &k) {
             const uint32_t t = trans_id(k, d);
             if (k.defer_at < 0 && lc::stream_defers((uint32_t)slot, (uint32_t)k.vals.size())) {
                 k.defer_at = (int64_t)k.ev.size();
-                ++s->n_deferred;
+                if (!s->set_tier) ++s->n_deferred;  // (set tier: counted when the key falls back)
             }
             k.ev.push_back(((uint32_t)enc << 24) | (t & 0xFFFFFFu));
             k.ev_row.push_back(h.row);
@@ -256,6 +270,13 @@ void touch(lc_stream *s, int32_t ki) {
     }
 }
 
+// A key that leaves the set tier (dead, in error, fallen back) gives its record back.
+void release_set(lc_stream *s, SKey &k) {
+    if (k.set_slot < 0) return;
+    lcst::stream_dev_set_free(s->dev, k.set_slot);
+    k.set_slot = -1;
+}
+
 // One row of key ki (A3 pairing, as host_pack.cpp pair_rows).
 void take_row(lc_stream *s, int32_t ki, const lc_history &h, int64_t r, int64_t row) {
     SKey &k = s->keys[(size_t)ki];
@@ -266,6 +287,7 @@ void take_row(lc_stream *s, int32_t ki, const lc_history &h, int64_t r, int64_t 
         if (!client_f(h.f[r], s->model)) {
             static const char *names[] = {"cas-register", "register", "mutex"};
             key_error(k, LC_E_UNSUPPORTED, "row " + std::to_string(row) + ": " + names[s->model] + " cannot step this :f");
+            release_set(s, k);
             return;
         }
         const int32_t id = new_op(k, SOp{h.v0[r], h.v1[r], h.f[r], FATE_OPEN, -1});
@@ -282,6 +304,7 @@ void take_row(lc_stream *s, int32_t ki, const lc_history &h, int64_t r, int64_t 
         if (!open) {
             key_error(k, LC_E_INVALID,
                       "row " + std::to_string(row) + ": process completed an operation without a prior invocation");
+            release_set(s, k);
             return;
         }
         SOp &op = k.ops[(size_t)*open];
@@ -319,12 +342,23 @@ void fill_update(lc_stream *s, lc_stream_update *u, int64_t events) {
     u->invalid = s->invalid_now.empty() ? nullptr : s->invalid_now.data();
 }
 
+void fall_back(lc_stream *s, SKey &k) {
+    release_set(s, k);
+    if (!k.fell_back) ++s->n_deferred;
+    k.fell_back = true;
+}
+
 // The launch's dead keys into the verdicts; the first key in error (or -1).
 int64_t take_dead(lc_stream *s, uint32_t *why) {
     int64_t bad = -1;
     for (const lcst::Dead &d : s->dead) {
         if (d.key >= s->keys.size()) continue;
         SKey &k = s->keys[d.key];
+        if (d.status == lc::STREAM_SET_FALLBACK) {  // back to deferral: not dead, checked at finish
+            fall_back(s, k);
+            continue;
+        }
+        release_set(s, k);
         k.dead = true;
         if (d.status == lc::STREAM_INVALID) {
             k.valid = LC_INVALID;
@@ -347,30 +381,76 @@ int send_rows(lc_stream *s, int64_t *events) {
     s->items.clear();
     s->ev16.clear();
     s->trans.clear();
+    s->set_mig.clear();
+    s->set_items.clear();
+    s->ev32.clear();
     std::sort(s->touched.begin(), s->touched.end());
     for (int32_t ki : s->touched) {
         SKey &k = s->keys[(size_t)ki];
         k.touched = false;
         if (k.err || k.dead || !s->dev) continue;
         const uint64_t end = k.defer_at >= 0 ? (uint64_t)k.defer_at : (uint64_t)k.ev.size();
-        if (end <= k.sent) continue;
-        lcst::Item it;
+        const uint32_t tr_b = (uint32_t)s->trans.size();
+        if (end > k.sent) {
+            lcst::Item it;
+            it.key = ki;
+            it.ev_b = (uint32_t)s->ev16.size();
+            for (uint64_t j = k.sent; j < end; ++j) s->ev16.push_back(word16(k.ev[(size_t)j]));
+            it.ev_e = (uint32_t)s->ev16.size();
+            it.tr_b = tr_b;
+            it.ntr = (uint32_t)k.descs.size();
+            s->trans.insert(s->trans.end(), k.descs.begin(), k.descs.end());
+            it.ns = (uint32_t)k.vals.size();
+            s->items.push_back(it);
+            *events += (int64_t)(end - k.sent);
+            k.sent = end;
+        }
+        // past the register tier: the key migrates with its first words there,
+        // later words go to its set record
+        if (!s->set_tier || k.defer_at < 0 || k.fell_back || k.ev.size() <= k.sent) continue;
+        bool narrow = !lc::stream_set_falls_back(0, 0, 0, (uint32_t)k.vals.size());
+        for (size_t j = (size_t)k.sent; j < k.ev.size() && narrow; ++j)
+            narrow = (k.ev[j] & LC_EV_OK_BIT) || !lc::stream_set_falls_back(0, 0, LC_EV_SLOT(k.ev[j]), 0);
+        if (!narrow) {
+            fall_back(s, k);
+            continue;
+        }
+        if (k.set_slot < 0) {
+            int rc = lcst::stream_dev_set_alloc(s->dev, &k.set_slot);
+            if (rc) return rc;
+            lcst::SetMig m{};
+            m.key = ki;
+            m.slot = k.set_slot;
+            // descriptors of the ops pending at defer_at, by window slot
+            int32_t tr_of[64];
+            std::fill(tr_of, tr_of + 64, -1);
+            for (size_t j = 0; j < (size_t)k.defer_at; ++j) {
+                const uint32_t w = k.ev[j], sl = LC_EV_SLOT(w) & 63u;
+                tr_of[sl] = (w & LC_EV_OK_BIT) ? -1 : (int32_t)LC_EV_TRANS(w);
+            }
+            for (int sl = 0; sl < 64; ++sl) m.descs[sl] = tr_of[sl] >= 0 ? k.descs[(size_t)tr_of[sl]] : 0u;
+            s->set_mig.push_back(m);
+        }
+        lcst::SetItem it;
         it.key = ki;
-        it.ev_b = (uint32_t)s->ev16.size();
-        for (uint64_t j = k.sent; j < end; ++j) s->ev16.push_back(word16(k.ev[(size_t)j]));
-        it.ev_e = (uint32_t)s->ev16.size();
-        it.tr_b = (uint32_t)s->trans.size();
+        it.slot = k.set_slot;
+        it.ev_b = (uint32_t)s->ev32.size();
+        s->ev32.insert(s->ev32.end(), k.ev.begin() + (std::ptrdiff_t)k.sent, k.ev.end());
+        it.ev_e = (uint32_t)s->ev32.size();
+        if (s->trans.size() == tr_b) s->trans.insert(s->trans.end(), k.descs.begin(), k.descs.end());
+        it.tr_b = tr_b;
         it.ntr = (uint32_t)k.descs.size();
-        s->trans.insert(s->trans.end(), k.descs.begin(), k.descs.end());
-        it.ns = (uint32_t)k.vals.size();
-        s->items.push_back(it);
-        *events += (int64_t)(end - k.sent);
-        k.sent = end;
+        s->set_items.push_back(it);
+        *events += (int64_t)(k.ev.size() - k.sent);
+        k.sent = k.ev.size();
     }
     s->touched.clear();
-    if (!s->dev || s->items.empty()) return LC_OK;
+    if (!s->dev || (s->items.empty() && s->set_items.empty())) return LC_OK;
+    const lcst::SetWork sw{s->set_mig.data(), (int64_t)s->set_mig.size(), s->set_items.data(),
+                           (int64_t)s->set_items.size(), s->ev32.data(), s->ev32.size()};
     int rc = lcst::stream_dev_push(s->dev, (int64_t)s->keys.size(), s->items.data(), (int64_t)s->items.size(),
-                                   s->ev16.data(), s->ev16.size(), s->trans.data(), s->trans.size(), 0, &s->dead);
+                                   s->ev16.data(), s->ev16.size(), s->trans.data(), s->trans.size(), 0, &s->dead,
+                                   s->set_tier ? &sw : nullptr);
     if (rc) return rc;
     uint32_t why = 0;
     const int64_t bad = take_dead(s, &why);
@@ -401,8 +481,14 @@ void dev_times(lc_stream *s) {
 }  // namespace
 
 extern "C" int lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream **out) {
+    return lc_stream_open_opts(ctx, opts, nullptr, out);
+}
+
+extern "C" int lc_stream_open_opts(lc_ctx *ctx, const lc_pack_opts *opts, const lc_stream_opts *sopts, lc_stream **out) {
     if (!out) return lc::fail(LC_E_INVALID, "lc_stream_open: null out");
     *out = nullptr;
+    if (sopts && (sopts->flags & ~(uint32_t)LC_STREAM_SET_TIER))
+        return lc::fail(LC_E_INVALID, "lc_stream_open_opts: unknown flags 0x%x", sopts->flags);
     const int model = opts ? opts->model : LC_MODEL_CAS_REGISTER;
     if (model == LC_MODEL_MULTI_REGISTER)
         return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: multi-register has no register-tier search to resume");
@@ -417,6 +503,7 @@ extern "C" int lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream *
             return rc;
         }
     }
+    s->set_tier = s->dev && sopts && (sopts->flags & LC_STREAM_SET_TIER);
     *out = s;
     return LC_OK;
 }
@@ -490,7 +577,7 @@ extern "C" int lc_stream_finish(lc_stream *s, lc_stream_update *u) {
         std::vector<int32_t> dk;
         for (size_t ki = 0; ki < s->keys.size(); ++ki) {
             const SKey &k = s->keys[ki];
-            if (k.defer_at >= 0 && !k.err && !k.dead) dk.push_back((int32_t)ki);
+            if (k.defer_at >= 0 && !k.err && !k.dead && (!s->set_tier || k.fell_back)) dk.push_back((int32_t)ki);
         }
         if (!dk.empty() && s->ctx) {
             std::vector<uint64_t> ev_off(dk.size() + 1, 0);
@@ -707,6 +794,53 @@ extern "C" int lc_stream_record(lc_stream *s, int64_t i, uint32_t *out) {
     if (!out) return lc::fail(LC_E_INVALID, "lc_stream_record: null out");
     if (!s->dev) return lc::fail(LC_E_INVALID, "lc_stream_record: a packer-only stream has no device");
     return lcst::stream_dev_record(s->dev, i, out);
+}
+
+namespace {
+int tier_of(const lc_stream *s, const SKey &k) {
+    if (k.err || k.dead) return LC_STREAM_TIER_DEAD;
+    if (k.defer_at < 0) return LC_STREAM_TIER_REGISTER;
+    return s->set_tier && !k.fell_back ? LC_STREAM_TIER_SET : LC_STREAM_TIER_FALLEN_BACK;
+}
+}  // namespace
+
+extern "C" int lc_stream_key_tier(const lc_stream *s, int64_t i) {
+    STREAM_KEY("lc_stream_key_tier");
+    return tier_of(s, k);
+}
+
+extern "C" int lc_stream_tiers(const lc_stream *s, int64_t *out4) {
+    if (!s || !out4) return lc::fail(LC_E_INVALID, "lc_stream_tiers: null argument");
+    out4[0] = out4[1] = out4[2] = out4[3] = 0;
+    for (const SKey &k : s->keys) ++out4[tier_of(s, k)];
+    return LC_OK;
+}
+
+extern "C" int64_t lc_stream_set_record(lc_stream *s, int64_t i, uint32_t *out, int64_t cap) {
+    STREAM_KEY("lc_stream_set_record");
+    if (!s->dev || k.set_slot < 0) return lc::fail(LC_E_INVALID, "lc_stream_set_record: key %lld has no set record", (long long)i);
+    uint32_t head[lc::STREAM_SET_OFF_S0];
+    int rc = lcst::stream_dev_set_record(s->dev, k.set_slot, 0, head, lc::STREAM_SET_OFF_S0);
+    if (rc) return rc;
+    const int64_t n_s = std::min<uint32_t>(head[lc::STREAM_SET_H_NS], lc::STREAM_SET_CAP);
+    const int64_t all = (int64_t)lc::STREAM_SET_OFF_S0 + 2 * n_s;
+    if (out && cap > 0) {
+        std::memcpy(out, head, (size_t)std::min<int64_t>(cap, lc::STREAM_SET_OFF_S0) * 4);
+        const int64_t more = std::min(cap, all) - (int64_t)lc::STREAM_SET_OFF_S0;
+        if (more > 0) {
+            rc = lcst::stream_dev_set_record(s->dev, k.set_slot, lc::stream_set_off_s(head[lc::STREAM_SET_H_CUR] & 1u),
+                                             out + lc::STREAM_SET_OFF_S0, more);
+            if (rc) return rc;
+        }
+    }
+    return all;
+}
+
+extern "C" int lc_stream_set_stats(const lc_stream *s, double *out6) {
+    if (!s || !out6) return lc::fail(LC_E_INVALID, "lc_stream_set_stats: null argument");
+    for (int i = 0; i < 6; ++i) out6[i] = 0;
+    if (s->dev) lcst::stream_dev_set_stats(s->dev, out6);
+    return LC_OK;
 }
 
 extern "C" int lc_stream_last_timing(const lc_stream *s, double *out_ms4) {

@@ -80,4 +80,52 @@ constexpr bool stream_defers(uint32_t slot, uint32_t states) {
 // a 16-bit event word.
 constexpr uint32_t STREAM_MAX_DESC = 1 + 32 + 32 + 32 * 32;
 
+// ---- the resident set tier (LC_STREAM_SET_TIER; device_stream_set.hip) ---------
+// A key that leaves the register tier keeps being searched from a set record
+// in device memory: the JIT search's config set S between two events, in the
+// narrow form of device_search.hip (state << 56 | window-slot bits of the ops
+// linearized and still pending), and each pending op's descriptor by window
+// slot.  The record, in 32-bit words: a header, 64 descriptors, two S arrays
+// of STREAM_SET_CAP u64 configs that an :ok reads and writes in turn.
+constexpr uint32_t STREAM_SET_HDR_WORDS = 16;
+constexpr uint32_t STREAM_SET_H_STATUS = 0;  // STREAM_LIVE / _INVALID / _ERROR / STREAM_SET_FALLBACK
+constexpr uint32_t STREAM_SET_H_NS = 1;      // configs in the current S array
+constexpr uint32_t STREAM_SET_H_PEND0 = 2;   // window slots 0..31 pending
+constexpr uint32_t STREAM_SET_H_PEND1 = 3;   // window slots 32..63
+constexpr uint32_t STREAM_SET_H_DONE = 4;    // events searched so far (register tier's included)
+constexpr uint32_t STREAM_SET_H_FAIL = 5;    // STREAM_INVALID: ordinal of the failing :ok in the key's stream
+constexpr uint32_t STREAM_SET_H_CUR = 6;     // which S array is current (0 / 1)
+constexpr uint32_t STREAM_SET_FALLBACK = 3;  // status: the key left the set tier for lc_stream_finish
+
+constexpr uint32_t STREAM_SET_SLOTS = 64;    // descriptors, one per window slot
+// Configs per S array, and the most the closure I of one :ok may hold.  At
+// most the smallest budget a stream accepts, so that a one-shot check that
+// gives up at its budget is never answered by the set tier;
+// at least a full register-tier lattice, so that every migration fits.
+constexpr uint32_t STREAM_SET_CAP = 32768;
+static_assert(STREAM_SET_CAP <= STREAM_MIN_BUDGET, "the set tier's cap is at most the least budget of a stream");
+static_assert(STREAM_SET_CAP >= STREAM_LATTICE_MAX * STREAM_MAX_STATES, "a full lattice migrates without loss");
+
+constexpr uint32_t STREAM_SET_OFF_DESC = STREAM_SET_HDR_WORDS;
+constexpr uint32_t STREAM_SET_OFF_S0 = STREAM_SET_OFF_DESC + STREAM_SET_SLOTS;
+constexpr uint32_t STREAM_SET_OFF_S1 = STREAM_SET_OFF_S0 + 2 * STREAM_SET_CAP;
+constexpr uint32_t STREAM_SET_REC_WORDS = STREAM_SET_OFF_S1 + 2 * STREAM_SET_CAP;
+static_assert(STREAM_SET_OFF_S0 % 2 == 0 && STREAM_SET_REC_WORDS % 2 == 0, "the S arrays are 8-byte aligned");
+constexpr uint32_t stream_set_off_s(uint32_t which) { return which ? STREAM_SET_OFF_S1 : STREAM_SET_OFF_S0; }
+// One slot of the set-record pool, bytes.
+constexpr uint64_t stream_set_slot_bytes() { return (uint64_t)STREAM_SET_REC_WORDS * 4; }
+
+// The narrow config's reach (include/lincheck.h LC_NARROW_MAX_SLOTS / _STATES).
+constexpr uint32_t STREAM_SET_MAX_SLOTS = 56;
+constexpr uint32_t STREAM_SET_MAX_STATES = 255;
+
+// Fallback: a migrated key returns to deferral -- its record is released and
+// lc_stream_finish checks it once, from its first event -- when an :ok's S'
+// (n_s) or closure I (n_i) would pass the cap, an invoke takes window slot
+// `slot` at or past the narrow form's, or the key has interned `states`
+// states, more than a narrow config's state field holds.
+constexpr bool stream_set_falls_back(uint64_t n_s, uint64_t n_i, uint32_t slot, uint32_t states) {
+    return n_s > STREAM_SET_CAP || n_i > STREAM_SET_CAP || slot >= STREAM_SET_MAX_SLOTS || states > STREAM_SET_MAX_STATES;
+}
+
 }  // namespace lc

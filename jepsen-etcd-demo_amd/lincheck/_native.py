@@ -167,6 +167,13 @@ class LcPerfResult(C.Structure):
 
 # ---- incremental check (lc_stream_*) -------------------------------------------
 LC_STREAM_REC_WORDS = 1360
+LC_STREAM_SET_TIER = 1
+LC_STREAM_TIER_REGISTER, LC_STREAM_TIER_SET, LC_STREAM_TIER_FALLEN_BACK, LC_STREAM_TIER_DEAD = 0, 1, 2, 3
+LC_STREAM_SET_HEAD_WORDS = 80
+
+
+class LcStreamOpts(C.Structure):
+    _fields_ = [("flags", C.c_uint32)]
 
 
 class LcStreamUpdate(C.Structure):
@@ -254,6 +261,11 @@ SIGNATURES = {
     "lc_perf_hist_name": (C.c_char_p, [C.c_void_p, C.c_int64]),
     "lc_perf_hist_free": (None, [C.c_void_p]),
     "lc_stream_open": (C.c_int, [C.c_void_p, P(LcPackOpts), P(C.c_void_p)]),
+    "lc_stream_open_opts": (C.c_int, [C.c_void_p, P(LcPackOpts), P(LcStreamOpts), P(C.c_void_p)]),
+    "lc_stream_key_tier": (C.c_int, [C.c_void_p, C.c_int64]),
+    "lc_stream_tiers": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_stream_set_record": (C.c_int64, [C.c_void_p, C.c_int64, P(C.c_uint32), C.c_int64]),
+    "lc_stream_set_stats": (C.c_int, [C.c_void_p, P(C.c_double)]),
     "lc_stream_append": (C.c_int, [C.c_void_p, P(LcHistory), P(LcStreamUpdate)]),
     "lc_stream_push": (C.c_int, [C.c_void_p, P(LcBatch), P(C.c_int64), P(LcStreamUpdate)]),
     "lc_stream_finish": (C.c_int, [C.c_void_p, P(LcStreamUpdate)]),

@@ -536,14 +536,16 @@ class Linearizable:
     def _dev(self) -> Device:
         return device_for(self.device, self.budget, self.algorithm)
 
-    def stream(self, dev: Optional[Device] = None):
+    def stream(self, dev: Optional[Device] = None, set_tier: bool = False):
         """An incremental check of this checker's model (lincheck.stream.Stream):
         rows are appended while the test runs and verdicts come back online.
+        set_tier: keys past the register tier keep being searched online too.
         :algorithm :wgl has no resident search and raises."""
         from .stream import Stream
         if self.algorithm == N.LC_ALGO_WGL:
             raise NotImplementedError("a stream runs the :linear search; :wgl has no state to resume")
-        return Stream(dev if dev is not None else device_for(self.device, self.budget, N.LC_ALGO_LINEAR), self.model)
+        return Stream(dev if dev is not None else device_for(self.device, self.budget, N.LC_ALGO_LINEAR), self.model,
+                      set_tier=set_tier)
 
     def check(self, test: Dict, history, opts: Dict | None = None) -> Dict:
         """One key's (unwrapped) sub-history, as at etcdemo.clj:117."""

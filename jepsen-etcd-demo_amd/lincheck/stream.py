@@ -16,6 +16,11 @@ counterexample of a key found invalid, run the ordinary checker
 (`checker.linearizable(...).check`) on that key's sub-history.
 `failing_row(i)` names the history row of the :ok that could not be linearized.
 
+`Stream(dev, set_tier=True)` keeps a key that passes 10 pending ops or 32
+register values on the device too (the resident set tier): it is reported
+online like the others instead of at `finish`; `tiers()` / `key_tier(i)` say
+where each key is searched.
+
 Models: cas-register, register and mutex.  (model/multi-register) and
 :algorithm :wgl have no register-tier search to resume and raise.
 """
@@ -56,14 +61,21 @@ class Stream:
     """A resident search on `dev` (a checker.Device), or a packer-only stream
     (dev None: no device is needed, only the accessors work)."""
 
-    def __init__(self, dev=None, model=None):
+    TIERS = ("register", "set", "fallen_back", "dead")
+
+    def __init__(self, dev=None, model=None, set_tier=False):
+        """set_tier: a key that leaves the register tier (10 ops pending, 32
+        states) migrates to the resident set tier and keeps being searched
+        online, instead of waiting for `finish` (LC_STREAM_SET_TIER)."""
         self.model = model if model is not None else CASRegister()
         if isinstance(self.model, MultiRegister):
             raise NotImplementedError("a stream checks (model/cas-register), (model/register) and (model/mutex)")
         self.dev = dev  # keeps the context alive
         opts = N.LcPackOpts(self.model.code)
         h = C.c_void_p()
-        N.check(N.lib().lc_stream_open(dev.handle if dev is not None else None, C.byref(opts), C.byref(h)))
+        sopts = N.LcStreamOpts(N.LC_STREAM_SET_TIER if set_tier else 0)
+        N.check(N.lib().lc_stream_open_opts(dev.handle if dev is not None else None, C.byref(opts), C.byref(sopts),
+                                            C.byref(h)))
         self.handle = h
 
     def close(self):
@@ -165,6 +177,35 @@ class Stream:
         out = np.zeros(N.LC_STREAM_REC_WORDS, np.uint32)
         N.check(N.lib().lc_stream_record(self.handle, i, N.ptr(out, C.c_uint32)))
         return out
+
+    def key_tier(self, i: int) -> str:
+        """Where key i is searched: "register", "set", "fallen_back" (checked
+        at `finish`, from its first event) or "dead" (invalid or in error)."""
+        return self.TIERS[int(N.check(N.lib().lc_stream_key_tier(self.handle, i)))]
+
+    def tiers(self) -> dict:
+        """Keys in each tier."""
+        out = np.zeros(4, np.int64)
+        N.check(N.lib().lc_stream_tiers(self.handle, N.ptr(out, C.c_int64)))
+        return dict(zip(self.TIERS, map(int, out)))
+
+    def set_record(self, i: int) -> dict:
+        """Key i's set record (diagnostics; layout: csrc/stream_plan.hpp): the
+        header words, the descriptors by window slot and the current configs
+        (state << 56 | window-slot bits)."""
+        n = int(N.check(N.lib().lc_stream_set_record(self.handle, i, None, 0)))
+        out = np.zeros(n, np.uint32)
+        N.check(N.lib().lc_stream_set_record(self.handle, i, N.ptr(out, C.c_uint32), n))
+        hw = N.LC_STREAM_SET_HEAD_WORDS
+        cfg = out[hw:].astype(np.uint64)
+        return {"header": out[:16], "descs": out[16:hw], "configs": cfg[0::2] | (cfg[1::2] << np.uint64(32))}
+
+    def set_stats(self) -> dict:
+        """The last call's set-tier device times and the set-record pool."""
+        out = np.zeros(6, np.float64)
+        N.check(N.lib().lc_stream_set_stats(self.handle, N.ptr(out, C.c_double)))
+        return {"migrate_ms": float(out[0]), "set_kernel_ms": float(out[1]), "pool_slots": int(out[2]),
+                "pool_in_use": int(out[3]), "pool_peak": int(out[4]), "slot_bytes": int(out[5])}
 
     def last_timing(self) -> dict:
         out = np.zeros(4, np.float64)

@@ -6,6 +6,13 @@ Shapes:
   (b) C2's history merged round-robin (one row of each key in turn, 2 M rows),
       in 20 and in 200 appends
   (c) a C3-shard-sized history (12,500 keys x 2,000 ops), in 20 appends
+  (d) 100 keys x 100 ops under the partition nemesis with 2% crashed ops (keys
+      leave the register tier), 100 rows per append, the resident set tier
+      (set_tier) on and off, alternating: what resuming costs against
+      restarting once at finish, the device time split into k_stream, the
+      migrations and k_stream_set, the share of leaving keys that fall back,
+      and the set-record pool's bytes.  --d-info-rate 0.05: the history whose
+      sets grow past the cap.
 
 Per append: the host clock around the call, and the library's own split
 (lc_stream_last_timing): host packing, then device events around the upload,
@@ -90,13 +97,14 @@ def state_bytes(s, searched_after):
     return rd, wr
 
 
-def run_stream(dev, h, n_appends, want=None, bytes_too=False):
+def run_stream(dev, h, n_appends, want=None, bytes_too=False, set_tier=False):
     import numpy as np
     from lincheck.stream import Stream
     n = len(h)
     step = -(-n // n_appends)
-    s = Stream(dev)
+    s = Stream(dev, set_tier=set_tier)
     per, searched = [], []
+    pool_peak = 0
     for lo in range(0, n, step):
         part = rows(h, lo, min(n, lo + step))
         t0 = time.perf_counter()
@@ -104,6 +112,10 @@ def run_stream(dev, h, n_appends, want=None, bytes_too=False):
         wall = (time.perf_counter() - t0) * 1e3
         t = s.last_timing()
         per.append(dict(wall_ms=wall, events=up.events, rows_held=up.rows_held, **t))
+        if set_tier:
+            st = s.set_stats()
+            per[-1].update(migrate_ms=st["migrate_ms"], set_kernel_ms=st["set_kernel_ms"])
+            pool_peak = max(pool_peak, st["pool_in_use"])
         if bytes_too:
             searched.append([s.key_events(i)["searched"] for i in range(up.n_keys)])
     t0 = time.perf_counter()
@@ -115,6 +127,13 @@ def run_stream(dev, h, n_appends, want=None, bytes_too=False):
             np.array_equal(res.cause, want.cause), "stream records differ from the one-shot check"
     out = dict(appends=len(per), finish_ms=fin, n_deferred=up.n_deferred, total_ms=sum(p["wall_ms"] for p in per) + fin,
                events=sum(p["events"] for p in per), per_append=per)
+    if set_tier:
+        st, t = s.set_stats(), s.tiers()
+        left = sum(s.key_events(i)["deferred_at"] >= 0 for i in range(len(res.keys)))
+        out.update(tiers=t, keys_left_register_tier=left, fallback_share=(t["fallen_back"] / left if left else 0.0),
+                   pool=dict(slot_bytes=st["slot_bytes"], slots_allocated=st["pool_slots"], peak_in_use=st["pool_peak"],
+                             peak_bytes=st["pool_peak"] * st["slot_bytes"],
+                             allocated_bytes=st["pool_slots"] * st["slot_bytes"]))
     if bytes_too:
         searched.append([s.key_events(i)["searched"] for i in range(len(res.keys))])
         rd, wr = state_bytes(s, searched[:-1] if len(searched) > len(per) else searched)
@@ -189,6 +208,32 @@ def shape_c(dev, reps):
     return dict(shape="c", rows=len(h), runs=[digest(r) for r in runs])
 
 
+def shape_d(dev, reps, info_rate):
+    """Set tier on and off, alternating; off is the stream as it was (restart at finish)."""
+    from lincheck import history as H
+    h = H.synth(n_keys=100, ops_per_key=100, concurrency=10, interleave=True, nemesis_period=5.0, info_rate=info_rate,
+                anomaly_rate=0.1, seed=11 if info_rate == 0.02 else 12)
+    _, want = one_shot(dev, h)
+    n_app = -(-len(h) // 100)
+    for on in (True, False):  # warm-up of both forms
+        run_stream(dev, h, n_app, want, set_tier=on)
+    out = dict(shape="d", rows=len(h), rows_per_append=100, info_rate=info_rate, forms={"set_tier_on": [], "set_tier_off": []})
+    for _ in range(reps):
+        for on in (True, False):
+            run = run_stream(dev, h, n_app, want, set_tier=on)
+            d = digest(run)
+            if on:
+                for k in ("migrate_ms", "set_kernel_ms"):
+                    d[k] = summary(p[k] for p in run["per_append"])
+                    d[k]["sum"] = sum(p[k] for p in run["per_append"])
+                d["kernel_ms"]["sum"] = sum(p["kernel_ms"] for p in run["per_append"])
+                d.update({k: run[k] for k in ("tiers", "keys_left_register_tier", "fallback_share", "pool")})
+            out["forms"]["set_tier_on" if on else "set_tier_off"].append(d)
+    out["totals_ms"] = {f: summary(x["total_ms"] for x in out["forms"][f]) for f in out["forms"]}
+    out["finish_ms"] = {f: summary(x["finish_ms"] for x in out["forms"][f]) for f in out["forms"]}
+    return out
+
+
 def profile():
     """k_stream's row of rocprofv3 --kernel-trace --stats, in a run of its own."""
     d = tempfile.mkdtemp(prefix="stream_prof_")
@@ -207,6 +252,7 @@ def main():
     ap.add_argument("--shapes", default="a,b,c")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--appends", default="20,200", help="shape b: the append counts")
+    ap.add_argument("--d-info-rate", type=float, default=0.02, help="shape d: 0.02 (seed 11) or 0.05 (seed 12)")
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_timing.json"))
     a = ap.parse_args()
@@ -223,6 +269,8 @@ def main():
             doc["shapes"].append(shape_b(dev, a.reps, tuple(int(x) for x in a.appends.split(","))))
         elif sh == "c":
             doc["shapes"].append(shape_c(dev, a.reps))
+        elif sh == "d":
+            doc["shapes"].append(shape_d(dev, a.reps, a.d_info_rate))
         print(json.dumps({k: v for k, v in doc["shapes"][-1].items() if k != "forms"})[:2000], flush=True)
     if a.profile:
         try:
