@@ -1,5 +1,7 @@
 // device_api.hip -- host orchestration of the device search (C ABI: lc_create,
-// lc_upload, lc_check_device, lc_check_batch, lc_check_node; include/lincheck.h).
+// lc_upload, lc_check_device, lc_check_batch, lc_wait; include/lincheck.h).
+// The context's types are in device_ctx.hpp, the node steps (lc_check_node*)
+// in device_node.hip, the device half of lc_stream_* in device_stream.hip.
 //
 // This is the native side of the drop-in at etcdemo.clj:115-119: one call
 // checks every key of a batch.  independent/checker's per-key pmap becomes
@@ -13,82 +15,20 @@
 // the register tier, which T0 checks itself as it walks the events (a
 // malformed event stops its key and the call returns LC_E_INVALID).
 
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
 #include <dlfcn.h>
 
-#include <algorithm>
+#include <atomic>
 #include <chrono>
-#include <condition_variable>
 #include <cstring>
 #include <functional>
-#include <mutex>
-#include <numeric>
 #include <string>
 #include <thread>
-#include <vector>
 
-#include "common.hpp"
-#include "device_search.hpp"
-#include "device_perf.hpp"
-#include "device_set.hpp"
-#include "device_stream.hpp"
-#include "step_plan.hpp"
-#include "lane_plan.hpp"
-#include "stream_plan.hpp"
+#include "device_ctx.hpp"
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t _e = (expr);                                                            \
-        if (_e != hipSuccess)                                                              \
-            return lc::fail(LC_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));  \
-    } while (0)
+using namespace lcx;
 
-// a step of ours that failed: its code goes up as it is (lc::fail has the message)
-#define LCCHK(expr)            \
-    do {                       \
-        int _rc = (expr);      \
-        if (_rc) return _rc;   \
-    } while (0)
-
-#define RCCLCHK(expr)                                                                     \
-    do {                                                                                   \
-        ncclResult_t _r = (expr);                                                          \
-        if (_r != ncclSuccess)                                                             \
-            return lc::fail(LC_E_DEVICE, "%s failed: %s", #expr, R->error(_r));            \
-    } while (0)
-
-namespace {
-
-constexpr int MAX_DEV = LC_MAX_DEVICES;
-
-template <class T>
-hipError_t dalloc(T **p, size_t n) {
-    *p = nullptr;
-    if (n == 0) n = 1;
-    return hipMalloc((void **)p, n * sizeof(T));
-}
-
-template <class T>
-void dfree(T *&p) {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-}
-
-// RCCL, loaded on first use from the directory of the HIP runtime this
-// library is bound to (a process may hold two: torch bundles its own), so
-// the communicator and our streams belong to one runtime.
-struct Rccl {
-    void *h = nullptr;
-    decltype(&ncclGetUniqueId) get_unique_id = nullptr;
-    decltype(&ncclCommInitRank) comm_init_rank = nullptr;
-    decltype(&ncclCommDestroy) comm_destroy = nullptr;
-    decltype(&ncclAllGather) all_gather = nullptr;
-    decltype(&ncclGetErrorString) error_string = nullptr;
-    const char *error(ncclResult_t r) const { return error_string ? error_string(r) : "rccl error"; }
-};
-
-const Rccl *rccl() {
+const Rccl *lcx::rccl() {
     static Rccl r;
     static std::once_flag once;
     std::call_once(once, [] {
@@ -111,6 +51,8 @@ const Rccl *rccl() {
     });
     return r.h ? &r : nullptr;
 }
+
+namespace {
 
 // 16-bit event words (lc_batch.events16) widened to the 32-bit form every
 // kernel reads (LC_EV16_WIDE): 4 words per thread, 8-byte loads, 16-byte stores.
@@ -144,91 +86,6 @@ __global__ void k_take_err(int32_t *words, uint32_t mask, int32_t *out) {
 
 using lc::HostPool;
 
-// One device's part of a batch in HBM.
-struct DevBatch {
-    int device = 0;
-    int64_t n_keys = 0;
-    uint64_t n_events = 0;
-    int64_t n_trans = 0;
-    uint32_t init_state = 0;
-    uint32_t shared_states = 0;  // 1 + largest state id in a shared table
-    bool has_trans_off = false;
-    uint64_t *ev_off = nullptr;
-    uint32_t *events = nullptr;
-    uint32_t *trans = nullptr;
-    uint32_t *trans_off = nullptr;
-    uint8_t *key_width = nullptr;
-    uint16_t *key_states = nullptr;
-    uint8_t *key_error = nullptr;
-    uint16_t *table = nullptr; // a table model's rows (lc_batch.table), or null
-    int64_t n_table = 0;
-    int32_t *order = nullptr;  // LPT: keys by event count, descending
-    bool t0_only = false;      // every key declared to fit the register lattice
-    bool taggable = false;     // keys may be cut into segments (shared table, states 0..5, no op installs nil)
-    bool seg_pays = false;     // sampled keys have quiescent points close enough for segments to pay
-    bool validated = false;    // the host checked every event (else the device does: T0_STRICT or k_validate<true>)
-    int64_t narrow_keys = 0;   // keys with at most 24 window slots (key_width): the WGL walk's LDS cache tier
-    // Device storage behind the arrays above, grown on demand: a batch that is
-    // re-uploaded (a context's staging batch for lc_check_batch) keeps it, so
-    // a host-to-host check allocates nothing once its sizes have been seen.
-    struct Mem {
-        void *p = nullptr;
-        size_t cap = 0;
-    } mem[8];
-    // pinned host staging of the per-key arrays and the transition table
-    // (one copy per upload); `hmeta_done` marks the end of the last copy out
-    // of it, so it is not rewritten while that copy may still read it
-    char *hmeta = nullptr;
-    size_t hmeta_cap = 0;
-    hipEvent_t hmeta_done = nullptr;
-    uint16_t *events16 = nullptr;    // 16-bit event words (mem[3]), or null: a register-tier batch
-                                     // uploaded at 2 bytes per event (lc_batch.events16)
-    mutable bool ev32_ready = true;  // `events` holds the 32-bit words (else widened, once, by the
-                                     // first step whose kernels read them: all but k_spec)
-    // the LPT order of the last upload and the offsets it was computed from
-    // (a batch re-uploaded with the same offsets reuses it)
-    std::vector<uint64_t> order_off;
-    std::vector<int32_t> order_of;
-    ~DevBatch() {
-        if (hmeta_done) (void)hipEventSynchronize(hmeta_done);
-        for (Mem &m : mem)
-            if (m.p) (void)hipFree(m.p);
-        if (hmeta) (void)hipHostFree(hmeta);
-        if (hmeta_done) (void)hipEventDestroy(hmeta_done);
-    }
-};
-
-struct lc_dev_batch {
-    int n_parts = 0;
-    int64_t n_keys = 0;
-    int64_t key0[MAX_DEV + 1] = {};  // part g holds keys [key0[g], key0[g + 1])
-    DevBatch *part[MAX_DEV] = {};
-    ~lc_dev_batch() {
-        for (DevBatch *p : part)
-            if (p) {
-                (void)hipSetDevice(p->device);
-                delete p;
-            }
-    }
-};
-
-// Point p at m's storage, growing it to hold n elements of T.
-template <class T>
-static hipError_t grow(DevBatch::Mem &m, T *&p, size_t n) {
-    const size_t bytes = std::max<size_t>(n, 1) * sizeof(T);
-    if (bytes > m.cap) {
-        if (m.p) (void)hipFree(m.p);
-        m.p = nullptr;
-        m.cap = 0;
-        p = nullptr;
-        hipError_t e = hipMalloc(&m.p, bytes);
-        if (e != hipSuccess) return e;
-        m.cap = bytes;
-    }
-    p = (T *)m.p;
-    return hipSuccess;
-}
-
 constexpr size_t CTL_BYTES = 4 * sizeof(unsigned long long) + 16 * sizeof(int32_t);
 // Beyond CTL_BYTES in the 256-byte control block: counters[16..19] the WGL
 // step's, [20] the keys a competition step hands to WGL, [24..31] the error words of the last 4 LC_DEV_ASYNC steps (slot =
@@ -238,217 +95,12 @@ constexpr int ERR_RING = 24, ERR_TAKEN = 32;
 // Most device memory the speculative segments' per-key workspaces may take.
 constexpr uint64_t SPEC_WS_MAX_BYTES = 8ull << 30;
 
-// What a search step reaches through stream order, one copy per search
-// lane: consecutive enqueued register-tier steps of lc_check_node_async
-// search on the two lanes in turn and overlap (lane_plan.hpp); every other
-// step runs on lane 0, after joining lane 1.
-struct Lane {
-    hipStream_t stream = nullptr;
-    // a step's verdicts when its results stay in the context (RES_CTX, RES_HOST)
-    int8_t *valid = nullptr;
-    int32_t *fail_event = nullptr;
-    uint8_t *cause = nullptr;
-    // speculative segments: each wave's 9-10-pending workspace, the rerun list
-    uint32_t *spec_ws = nullptr;
-    size_t spec_ws_words = 0;
-    uint32_t *spec_fin = nullptr;  // exact speculative segments: each run's saved set
-    size_t spec_fin_words = 0;
-    int32_t *spec_rr = nullptr;    // two rerun counts (used in turn), then the rerun list
-    int64_t spec_rr_cap = 0;
-    int spec_parity = 0;
-    // Device copies of T0's Args (read once per key): a ring of 12, so steps
-    // alternating between result sets (the N > 1 bench), or pipelined steps
-    // between their staging batches and error words (3 x 4 in turn on one
-    // lane, 3 x 2 on each of two), each find theirs without a copy; a slot's
-    // pinned staging copy is rewritten only after the copy out of it
-    // (args_ev) has run.
-    static constexpr int ARGS_RING = 12;
-    lcd::Args *dargs = nullptr;    // [ARGS_RING]
-    lcd::Args *hargs = nullptr;    // [ARGS_RING] pinned
-    hipEvent_t args_ev[ARGS_RING] = {};
-    bool args_ok[ARGS_RING] = {};
-    uint32_t args_next = 0;
-    // an overlapping step's records when they cannot go straight into the
-    // caller's buffer (a step still in flight was given it too)
-    uint64_t *rec = nullptr;
-    int64_t rec_cap = 0;
-    hipEvent_t done = nullptr;  // lane 1: everything enqueued on it, for lane 0 to join
-    void free_all() {
-        dfree(valid); dfree(fail_event); dfree(cause);
-        dfree(spec_ws); dfree(spec_rr); dfree(spec_fin); dfree(dargs); dfree(rec);
-        if (hargs) (void)hipHostFree(hargs);
-        hargs = nullptr;
-        for (hipEvent_t &e : args_ev) {
-            if (e) (void)hipEventDestroy(e);
-            e = nullptr;
-        }
-        if (done) (void)hipEventDestroy(done);
-        done = nullptr;
-    }
-};
-
-// One device of a context: its streams, scratch and result arrays.
-struct Dev {
-    const lc_opts *o = nullptr;  // the context's options
-    int device = 0;
-    int cu_count = 256;
-    hipStream_t stream = nullptr;   // lane 0's (lane[0].stream): every step but the overlapping ones' second
-    hipStream_t stream1 = nullptr;  // lane 1's: every second overlapping search; else the validation of
-                                    // host-unchecked batches, beside T0
-    Lane lane[lc::LANES];
-    bool lane1_live = false;        // lane 1 has work lane 0 has not joined
-    bool lane1_wait_start = false;  // lane 1's next search first waits for run_start
-    uint64_t run_n = 0;             // overlapping steps since the lanes were last joined
-    hipEvent_t run_start = nullptr; // lane 0, ahead of such a run's first search (its set-up done)
-    hipStream_t cstream = nullptr;  // lc_check_node's chunked uploads, ahead of the searches
-    hipStream_t estream = nullptr;  // lc_wait_step's error reads (behind no upload or step)
-    static constexpr int NODE_CHUNKS = 4;
-    DevBatch *chunk[NODE_CHUNKS] = {};
-    hipEvent_t chunk_ready[NODE_CHUNKS] = {};
-    hipEvent_t vin = nullptr, vdone = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr, et0 = nullptr, et3a = nullptr, et3b = nullptr;
-    hipEvent_t ea0 = nullptr, ea1 = nullptr;  // span of the LC_DEV_ASYNC steps since lc_wait
-    uint32_t n_async = 0;
-    bool ea1_pending = false;  // asynchronous steps enqueued since ea1 was last recorded
-    hipEvent_t ring[4] = {};  // end of each of the last 4 LC_DEV_ASYNC steps (lc_wait_step)
-    uint64_t async_seq = 0;
-    // scratch, grown on demand
-    int64_t cap_keys = 0;
-    int32_t *lists = nullptr;      // 5 x cap_keys: spill0, spill1, spill2, wide, old (T3L -> narrow T3)
-    // one 96-byte control block, zeroed and read back in one operation each:
-    // acc (4 x u64: probes, events, keys_done, T3L stream bytes) then counters (16 x i32:
-    // n_spill0, n_spill1, n_spill2, n_wide, err bits, 1 + bad key, n_old, -,
-    // tickets[8..15])
-    unsigned long long *ctl = nullptr;
-    unsigned long long *acc = nullptr;
-    int32_t *counters = nullptr;
-    unsigned long long *hctl = nullptr;  // pinned host copy of ctl
-    uint32_t *peak = nullptr;
-    uint64_t *final_cfg = nullptr;
-    uint32_t *n_final = nullptr;
-    DevBatch *staged = nullptr;    // lc_check_batch's staging batch (device arrays reused)
-    // T0-only steps skip re-zeroing the control block: the ticket continues
-    // from where the previous such step left it.
-    bool ticket_live = false;
-    uint32_t ticket_next = 0;
-    // key segments (register-tier steps of a batch of about one key per
-    // SIMD): per-key cut points, segment results, work lists
-    int64_t seg_keys = 0;
-    uint32_t *seg_cnt = nullptr, *seg_end = nullptr, *seg_out = nullptr, *seg_work = nullptr;
-    uint32_t *seg_rerun = nullptr, *seg_rerun_init = nullptr;
-    int32_t *seg0_fev = nullptr, *seg_ctl = nullptr;
-    // node records (lc_check_node): this rank's block and the gathered node
-    uint64_t *send = nullptr, *node = nullptr;
-    int64_t node_cap = 0, node_n = 0;
-    uint64_t *rec_out = nullptr;  // set around a node step's search: finish_key writes the records there
-    uint64_t *hnode = nullptr;  // pinned landing area of the node's records (lc_check_node)
-    int64_t hnode_cap = 0;
-    // lc_check_node_async: three staging batches used in turn, so a step's
-    // upload (on cstream) runs while the two steps before it search; pipe_ready
-    // = a slot's upload is done; the step that read a slot is done when its
-    // ring event (async_seq pipe_seq[s]) is; pipe_lo .. pipe_hi = the
-    // caller's record buffer that step was given
-    static constexpr int PIPE = lc::LANE_SLOTS;
-    DevBatch *pipe[PIPE] = {};
-    hipEvent_t pipe_ready[PIPE] = {};
-    uint64_t pipe_seq[PIPE] = {};
-    bool pipe_busy[PIPE] = {};
-    uint64_t pipe_lo[PIPE] = {}, pipe_hi[PIPE] = {};
-    uint64_t pipe_next = 0;
-    // T3 (HBM tier) workspaces: narrow / wide configs
-    struct Ws {
-        char *base = nullptr;
-        size_t bytes = 0;
-        int slots = 0;
-        lcd::HbmWs w{};
-    } ws[2];
-    // layered T3 workspace (device_layers.hip)
-    struct LWs {
-        char *base = nullptr;
-        size_t bytes = 0;
-        int slots = 0;
-        lcd::LayWs w{};
-    } lws;
-    // knossos.wgl workspaces (device_wgl.hip): [0] tables sized to share at
-    // most a share of the free HBM (WGL_SHARE_MAX), [1] tables the budget
-    // fits, for the keys that outgrow [0]; zeroed once (entries are stamped)
-    struct WWs {
-        char *base = nullptr;
-        size_t bytes = 0;
-        lcd::WglWs layout{};  // the layout its contents were written under
-        int slots = 0;
-    } wws[2];
-    uint32_t wgl_seq = 0;     // launches so far (the high half of every cache stamp)
-    uint8_t *analyzer = nullptr;  // [cap_keys] LC_ALGO_* that answered each key
-    lcs::SetDev *setdev = nullptr;  // lc_set_check's cached arrays (device_set.hip), made on first use
-    lcp::PerfDev *perfdev = nullptr;  // lc_perf_check's (device_perf.hip), likewise
-    ~Dev() {
-        (void)hipSetDevice(device);
-        if (stream) (void)hipStreamSynchronize(stream);
-        if (stream1) (void)hipStreamSynchronize(stream1);
-        lcs::set_dev_free(setdev);
-        lcp::perf_dev_free(perfdev);
-        dfree(lists); dfree(ctl);
-        if (hctl) (void)hipHostFree(hctl);
-        dfree(peak); dfree(final_cfg); dfree(n_final);
-        dfree(ws[0].base); dfree(ws[1].base); dfree(lws.base); dfree(send); dfree(node);
-        dfree(wws[0].base); dfree(wws[1].base); dfree(analyzer);
-        dfree(seg_cnt); dfree(seg_end); dfree(seg_out); dfree(seg_work); dfree(seg_rerun); dfree(seg_rerun_init);
-        dfree(seg0_fev); dfree(seg_ctl);
-        for (Lane &l : lane) l.free_all();
-        if (hnode) (void)hipHostFree(hnode);
-        delete staged;
-        for (int i = 0; i < PIPE; ++i) {
-            delete pipe[i];
-            for (hipEvent_t e : {pipe_ready[i]})
-                if (e) (void)hipEventDestroy(e);
-        }
-        for (int i = 0; i < NODE_CHUNKS; ++i) {
-            delete chunk[i];
-            if (chunk_ready[i]) (void)hipEventDestroy(chunk_ready[i]);
-        }
-        if (cstream) (void)hipStreamSynchronize(cstream);
-        if (cstream) (void)hipStreamDestroy(cstream);
-        if (estream) (void)hipStreamSynchronize(estream);
-        if (estream) (void)hipStreamDestroy(estream);
-        for (hipEvent_t e : {e0, e1, et0, et3a, et3b, ea0, ea1, vin, vdone, run_start})
-            if (e) (void)hipEventDestroy(e);
-        if (stream1) (void)hipStreamDestroy(stream1);
-        for (hipEvent_t &e : ring)
-            if (e) (void)hipEventDestroy(e);
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-struct lc_ctx {
-    lc_opts o{};
-    int n_dev = 0;
-    Dev *dev[MAX_DEV] = {};
-    std::mutex mu;                 // one call at a time (include/lincheck.h)
-    HostPool *pool = nullptr;      // validation / staging workers, created on first use
-    HostPool *drivers = nullptr;   // one thread per device beyond the first
-    uint32_t *hstage = nullptr;    // pinned copy of a batch's event words
-    size_t hstage_cap = 0;
-    // one process per GPU: RCCL communicator over the node's ranks
-    ncclComm_t comm = nullptr;
-    int rank = 0, size = 1;
-    ~lc_ctx() {
-        if (comm) {
-            (void)hipSetDevice(dev[0]->device);
-            (void)hipStreamSynchronize(dev[0]->stream);
-            if (const Rccl *R = rccl()) (void)R->comm_destroy(comm);
-        }
-        for (Dev *d : dev) delete d;
-        delete pool;
-        delete drivers;
-        if (hstage) (void)hipHostFree(hstage);
-    }
-};
-
 // Lane 0 behind everything enqueued on lane 1: whatever follows on lane 0
 // (any step but an overlapping one, a wait) sees all that was enqueued
 // before it.  The next run of overlapping steps starts on lane 0 again.
-static int join_lanes(Dev *c) {
+namespace lcx {
+
+int join_lanes(Dev *c) {
     if (c->lane1_live) {
         HIPCHK(hipEventRecord(c->lane[1].done, c->stream1));
         HIPCHK(hipStreamWaitEvent(c->stream, c->lane[1].done, 0));
@@ -459,7 +111,7 @@ static int join_lanes(Dev *c) {
 }
 
 // The host behind both lanes (before a buffer their steps use is freed).
-static int drain_lanes(Dev *c) {
+int drain_lanes(Dev *c) {
     HIPCHK(hipStreamSynchronize(c->stream1));
     HIPCHK(hipStreamSynchronize(c->stream));
     c->lane1_live = c->lane1_wait_start = false;
@@ -467,7 +119,7 @@ static int drain_lanes(Dev *c) {
     return LC_OK;
 }
 
-static int ensure_capacity(Dev *c, int64_t n_keys) {
+int ensure_capacity(Dev *c, int64_t n_keys) {
     if (n_keys <= c->cap_keys) return LC_OK;
     int64_t cap = std::max<int64_t>(n_keys, 1024);
     if (c->n_async) LCCHK(drain_lanes(c));  // an enqueued step may still write what goes
@@ -488,6 +140,8 @@ static int ensure_capacity(Dev *c, int64_t n_keys) {
     c->cap_keys = cap;
     return LC_OK;
 }
+
+}  // namespace lcx
 
 // Lay out (and if needed allocate) the layered T3 workspace for `want`
 // blocks: four arrays of budget + slack entries (8 B) per block.
@@ -832,18 +486,6 @@ static int validate_batch(const lc_batch *b) {
     return LC_OK;
 }
 
-// What the register tier needs to know of a batch before any upload: the
-// state count of a shared table and whether every key is declared to fit T0
-// (width, states, initial state).  A batch that does is validated by T0
-// itself (T0_STRICT), so the host skips its per-event pass.
-struct Shape {
-    uint32_t shared_states = 0;
-    bool t0_only = false;
-    bool taggable = false;  // segments (lcd::SegArgs): shared table, states 0..5 from nil, nothing installs nil
-    bool seg_pays = false;  // sampled keys: the longest stretch without a quiescent point is short
-    bool host_checked = false;  // prepare_batch walked every event (table models: their rows too)
-};
-
 // Would key segments pay?  A segment ends only at a quiescent point, so the
 // longest stretch without one bounds the segmented search, as the whole key
 // bounds the unsegmented one.  Up to 4 keys spread over the batch are
@@ -901,8 +543,10 @@ static Shape batch_shape(const lc_batch *b) {
     return s;
 }
 
+namespace lcx {
+
 // Is p page-locked host memory (a DMA source without a bounce)?
-static bool pinned(const void *p) {
+bool pinned(const void *p) {
     if (!p) return false;
     hipPointerAttribute_t at;
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -913,7 +557,7 @@ static bool pinned(const void *p) {
 }
 
 // Keys [k0, k1) of b as a batch of their own (ev_off rebased into `off`).
-static lc_batch sub_batch(const lc_batch *b, int64_t k0, int64_t k1, std::vector<uint64_t> &off) {
+lc_batch sub_batch(const lc_batch *b, int64_t k0, int64_t k1, std::vector<uint64_t> &off) {
     lc_batch s = *b;
     s.n_keys = k1 - k0;
     off.resize((size_t)(k1 - k0) + 1);
@@ -930,7 +574,7 @@ static lc_batch sub_batch(const lc_batch *b, int64_t k0, int64_t k1, std::vector
 }
 
 // Contiguous key shards of about equal event counts, one per device.
-static void shard_keys(const lc_batch *b, int n, int64_t *key0) {
+void shard_keys(const lc_batch *b, int n, int64_t *key0) {
     const int64_t K = b->n_keys;
     const uint64_t tot = K ? b->ev_off[K] : 0;
     key0[0] = 0;
@@ -949,8 +593,8 @@ static void shard_keys(const lc_batch *b, int n, int64_t *key0) {
 // event words are copied straight from the caller's (page-locked) memory.
 // sync: wait for the copies (the caller may free its arrays on return);
 // otherwise the caller keeps them alive until its stream has passed them.
-static int upload_into(Dev *c, const lc_batch *b, DevBatch *d, const Shape &sh, bool validated,
-                       const uint32_t *events_src = nullptr, bool sync = true, hipStream_t stream = nullptr) {
+int upload_into(Dev *c, const lc_batch *b, DevBatch *d, const Shape &sh, bool validated, const uint32_t *events_src,
+                bool sync, hipStream_t stream) {
     lc::Range range("lincheck: upload");
     hipStream_t cs = stream ? stream : c->stream;
     const int64_t K = b->n_keys;
@@ -1003,13 +647,7 @@ static int upload_into(Dev *c, const lc_batch *b, DevBatch *d, const Shape &sh, 
     const size_t bytes = al(o_err + (b->key_error ? Kz : 0));
     if (!d->hmeta_done) HIPCHK(hipEventCreateWithFlags(&d->hmeta_done, hipEventDisableTiming));
     HIPCHK(hipEventSynchronize(d->hmeta_done));  // the previous copy out of the block is done
-    if (bytes > d->hmeta_cap) {
-        if (d->hmeta) (void)hipHostFree(d->hmeta);
-        d->hmeta = nullptr;
-        d->hmeta_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&d->hmeta, bytes, hipHostMallocDefault));
-        d->hmeta_cap = bytes;
-    }
+    HIPCHK(grow_pinned(d->hmeta, d->hmeta_cap, bytes));
     char *h = d->hmeta;
     std::memcpy(h + o_off, b->ev_off, (Kz + 1) * 8);
     // LPT order: longest keys first (kept from the last upload when the
@@ -1053,6 +691,8 @@ static int upload_into(Dev *c, const lc_batch *b, DevBatch *d, const Shape &sh, 
     if (sync) HIPCHK(hipStreamSynchronize(cs));
     return LC_OK;
 }
+
+}  // namespace lcx
 
 // ---- one device's search ----------------------------------------------------
 
@@ -1263,8 +903,6 @@ static int run_wgl(Dev *c, const DevBatch *d, const lcd::Args &a, const int32_t 
     return LC_OK;
 }
 
-enum ResMode { RES_HOST = 0, RES_DEV = 1, RES_CTX = 2 };
-
 // One search step, as dev_search's stages see it: where it runs, its plan
 // (step_plan.hpp), the Args every launch of it shares, and what the tiers
 // leave for fill_stats.
@@ -1286,18 +924,7 @@ struct Step {
     uint64_t wgl_keys = 0, wgl_steps = 0, wgl_spilled = 0;
     Lane *L = nullptr;             // the lane whose scratch and result arrays the step uses
     hipStream_t q = nullptr;       // ... and its stream (lane 0's for every step but an overlapping one)
-    const struct LaneUse *lu = nullptr;
-};
-
-// How lc_check_node_async places an enqueued step (lane_plan.hpp): its lane,
-// and for records that go through the lane's block (Lane::rec) their download
-// -- n records to dst behind the searches' launches, once `after` has passed.
-struct LaneUse {
-    int lane = 0;
-    bool overlap = false;
-    uint64_t *dst = nullptr;
-    size_t n = 0;
-    hipEvent_t after = nullptr;
+    const LaneUse *lu = nullptr;
 };
 
 // The work lists between the tiers (Dev::lists) and their counts (Dev::counters).
@@ -1438,19 +1065,6 @@ static int search_wgl(Step &s, lc_stats *st) {
         st->probes = c->hctl[0];  // Lowe's cache lookups
         st->wgl_spilled = ws.wgl_spilled;
     }
-    return LC_OK;
-}
-
-// Grow a device buffer the speculative segments work in to `need` elements
-// (an enqueued step may still be using the one it replaces).
-template <class T, class N>
-static int grow_dev(Dev *c, T *&ptr, N &have, N need) {
-    if (need <= have) return LC_OK;
-    if (c->n_async) LCCHK(drain_lanes(c));
-    dfree(ptr);
-    have = 0;
-    HIPCHK(dalloc(&ptr, (size_t)need));
-    have = need;
     return LC_OK;
 }
 
@@ -1767,8 +1381,8 @@ static void fill_stats(const Step &s, lc_stats *st) {
 // lu: an overlapping step of lc_check_node_async and its lane (plan_lane's
 // choice, lane_plan.hpp); any other step runs on lane 0, behind everything
 // enqueued on either lane before it.
-static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mode, bool allow_async, int64_t key0,
-                      lc_stats *st, bool *enqueued = nullptr, int64_t res_off = 0, const LaneUse *lu = nullptr) {
+int lcx::dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mode, bool allow_async, int64_t key0,
+                    lc_stats *st, bool *enqueued, int64_t res_off, const LaneUse *lu) {
     lc::Range range("lincheck: search");
     if (enqueued) *enqueued = false;
     const auto t0 = std::chrono::steady_clock::now();
@@ -1839,7 +1453,7 @@ static int dev_search(Dev *c, const DevBatch *d, const lc_result *r, ResMode mod
 
 // Wait for everything enqueued on c; *n_async / *span_ms: the asynchronous
 // steps since the last wait and their HIP-event span.
-static int dev_wait(Dev *c, int *n_async, float *span_ms) {
+int lcx::dev_wait(Dev *c, int *n_async, float *span_ms) {
     lc::Range range("lincheck: wait");
     HIPCHK(hipSetDevice(c->device));
     // lane 0 behind lane 1: the span's end below is the later lane's, and
@@ -1898,7 +1512,7 @@ static int each_device(lc_ctx *c, const std::function<int(int)> &fn) {
 // Validate b (events too unless T0 will) and, when its event words are not
 // page-locked, copy them into the context's pinned staging buffer.  *src:
 // where the uploads read the events from (b->events or the staging copy).
-static int prepare_batch(lc_ctx *c, const lc_batch *b, Shape *sh, const uint32_t **src) {
+int lcx::prepare_batch(lc_ctx *c, const lc_batch *b, Shape *sh, const uint32_t **src) {
     lc::Range range("lincheck: prepare");
     int rc = validate_batch(b);
     if (rc) return rc;
@@ -1916,13 +1530,7 @@ static int prepare_batch(lc_ctx *c, const lc_batch *b, Shape *sh, const uint32_t
     const bool widen = n_ev > 0 && !b->events && !up16;
     const bool stage = widen || (n_ev > 0 && b->events && n_ev <= (256u << 20) / 4 && !pinned(b->events) &&
                                  !(up16 && pinned(b->events16)));
-    if (stage && n_ev > c->hstage_cap) {
-        if (c->hstage) (void)hipHostFree(c->hstage);
-        c->hstage = nullptr;
-        c->hstage_cap = 0;
-        HIPCHK(hipHostMalloc((void **)&c->hstage, n_ev * 4, hipHostMallocDefault));
-        c->hstage_cap = n_ev;
-    }
+    if (stage) HIPCHK(grow_pinned(c->hstage, c->hstage_cap, n_ev));
     // The device validates every event of a batch (k_validate beside the
     // first tier; the later tiers do nothing over a refused batch), so the
     // host walks the events only to stage pageable ones -- and to check a
@@ -2079,10 +1687,7 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
     std::vector<lc_stats> ps((size_t)c->n_dev);
     rc = each_device(c, [&](int p) {
         Dev *d = c->dev[p];
-        if (!d->staged) {
-            d->staged = new (std::nothrow) DevBatch();
-            if (!d->staged) return lc::fail(LC_E_NOMEM, "lc_check_batch: out of memory");
-        }
+        if (int e = staging_batch(d->staged, "lc_check_batch")) return e;
         std::vector<uint64_t> off;
         const lc_batch s = c->n_dev > 1 ? sub_batch(b, key0[p], key0[p + 1], off) : *b;
         const uint32_t *es = src ? src + (b->n_keys ? b->ev_off[key0[p]] : 0) : nullptr;
@@ -2105,328 +1710,11 @@ extern "C" int lc_check_batch(lc_ctx *c, const lc_batch *b, lc_result *r, lc_sta
     return LC_OK;
 }
 
-// ---- one process per GPU: node-wide verdict records ---------------------------
-
-// The rank's record block (and the node's), grown on demand; the search that
-// follows writes its records straight into the block (Dev::rec_out), and the
-// padding past the shard's n keys is zeroed.
-static int node_buffers(lc_ctx *x, Dev *c, int64_t n, int64_t block) {
-    if (block > c->node_cap || !c->send) {
-        if (c->n_async) LCCHK(drain_lanes(c));  // an enqueued step may still write them
-        dfree(c->send);
-        dfree(c->node);
-        HIPCHK(dalloc(&c->send, (size_t)std::max<int64_t>(block, 1)));
-        HIPCHK(dalloc(&c->node, (size_t)std::max<int64_t>(block, 1) * x->size));
-        c->node_cap = block;
-    }
-    uint64_t *blk = x->comm ? c->send : c->node;
-    if (block > n) HIPCHK(hipMemsetAsync(blk + n, 0, (size_t)(block - n) * 8, c->stream));
-    c->rec_out = blk;
-    return LC_OK;
-}
-
-// All-gather every rank's block (the records the search wrote) over RCCL on
-// c's stream; one rank: the block is the node.
-static int gather_node(lc_ctx *x, Dev *c, int64_t block) {
-    lc::Range range("lincheck: gather");
-    c->rec_out = nullptr;
-    if (x->comm) {
-        const Rccl *R = rccl();
-        RCCLCHK(R->all_gather(c->send, c->node, (size_t)block, ncclUint64, x->comm, c->stream));
-    }
-    c->node_n = block * x->size;
-    return LC_OK;
-}
-
-// Stops later searches writing records, on every return of a node step.
-struct RecOff {
-    Dev *d;
-    ~RecOff() { d->rec_out = nullptr; }
-};
-
-// A node step's error return: the copies out of the caller's arrays are waited for.
-static int drained(Dev *d, int e) {
-    (void)hipStreamSynchronize(d->cstream);
-    (void)hipStreamSynchronize(d->stream1);
-    (void)hipStreamSynchronize(d->stream);
-    d->lane1_live = d->lane1_wait_start = false;
-    d->run_n = 0;
-    return e;
-}
-
-// An overlapping step's record block on its lane (grown on demand), the
-// padding past the shard's n keys zeroed: the search writes its records
-// there, and they are copied out behind it (finish_async).
-static int lane_records(Dev *c, Lane &L, int64_t n, int64_t block) {
-    LCCHK(grow_dev(c, L.rec, L.rec_cap, std::max<int64_t>(block, 1)));
-    if (block > n) HIPCHK(hipMemsetAsync(L.rec + n, 0, (size_t)(block - n) * 8, L.stream));
-    c->rec_out = L.rec;
-    return LC_OK;
-}
-
-static int node_check_args(lc_ctx *c, int64_t n_keys, int64_t block) {
-    if (c->n_dev != 1) return lc::fail(LC_E_INVALID, "lc_check_node: needs a one-device context");
-    if (block < n_keys) return lc::fail(LC_E_INVALID, "lc_check_node: block %lld < the shard's %lld keys",
-                                        (long long)block, (long long)n_keys);
-    return LC_OK;
-}
-
-extern "C" int lc_check_node(lc_ctx *c, const lc_batch *b, int64_t block, uint64_t *node, lc_stats *st) {
-    lc::Range range("lc_check_node");
-    auto t0 = std::chrono::steady_clock::now();
-    if (!c || !b || !node) return lc::fail(LC_E_INVALID, "lc_check_node: null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = node_check_args(c, b->n_keys, block);
-    if (rc) return rc;
-    Shape sh;
-    const uint32_t *src = nullptr;
-    rc = prepare_batch(c, b, &sh, &src);
-    if (rc) return rc;
-    Dev *d = c->dev[0];
-    if (!d->staged) {
-        d->staged = new (std::nothrow) DevBatch();
-        if (!d->staged) return lc::fail(LC_E_NOMEM, "lc_check_node: out of memory");
-    }
-    rc = node_buffers(c, d, b->n_keys, block);
-    if (rc) return rc;
-    RecOff rec_off{d};
-    const auto t_prep = std::chrono::steady_clock::now();
-    // A large register-tier shard (throughput-bound: many keys per SIMD) is
-    // uploaded and searched in NODE_CHUNKS key chunks: the copies run on a
-    // stream of their own, and each chunk's search waits only for its own
-    // copy, so the host-to-device transfer overlaps the search
-    // (lc_opts.path_flags LC_PATH_CHUNKS_ON / _OFF pin the choice).
-    const int64_t K = b->n_keys;
-    const uint64_t n_ev = K ? b->ev_off[K] : 0;
-    const bool can_chunk = sh.t0_only && !(c->o.flags & LC_OPT_COUNT_PROBES) && K >= Dev::NODE_CHUNKS;
-    bool big = K >= 16 * (int64_t)d->cu_count && n_ev >= (8u << 20);
-    if (c->o.path_flags & LC_PATH_CHUNKS_ON) big = true;
-    if (c->o.path_flags & LC_PATH_CHUNKS_OFF) big = false;
-    // (Searching page-locked event words in place, over the host link, was
-    // measured slower: 0.468 against 0.332 ms for C2's search, the link
-    // sustaining ~31 GB/s of kernel reads; the 16-bit upload won instead.)
-    const int chunks = can_chunk && big ? Dev::NODE_CHUNKS : 1;
-    lc_result none{};
-    bool enq = false;
-    std::chrono::steady_clock::time_point t_up;
-    if (chunks > 1) {
-        rc = ensure_capacity(d, K);
-        if (rc) return rc;
-        int64_t key0[Dev::NODE_CHUNKS + 1];
-        shard_keys(b, chunks, key0);
-        for (int i = 0; i < chunks; ++i) {
-            if (!d->chunk[i]) {
-                d->chunk[i] = new (std::nothrow) DevBatch();
-                if (!d->chunk[i]) return drained(d, lc::fail(LC_E_NOMEM, "lc_check_node: out of memory"));
-            }
-            if (!d->chunk_ready[i]) HIPCHK(hipEventCreateWithFlags(&d->chunk_ready[i], hipEventDisableTiming));
-            std::vector<uint64_t> off;
-            const lc_batch s = sub_batch(b, key0[i], key0[i + 1], off);
-            const uint32_t *es = src ? src + b->ev_off[key0[i]] : nullptr;
-            rc = upload_into(d, &s, d->chunk[i], sh, sh.host_checked, es, false, d->cstream);
-            if (rc) return drained(d, rc);
-            HIPCHK(hipEventRecord(d->chunk_ready[i], d->cstream));
-        }
-        t_up = std::chrono::steady_clock::now();
-        for (int i = 0; i < chunks && rc == 0; ++i) {
-            HIPCHK(hipStreamWaitEvent(d->stream, d->chunk_ready[i], 0));
-            bool e = false;
-            rc = dev_search(d, d->chunk[i], &none, RES_CTX, true, key0[i], st, &e, key0[i]);
-            enq = i == 0 ? e : (enq && e);
-        }
-        if (rc) return drained(d, rc);
-        if (!enq) return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node: a chunk left the register tier"));
-    } else {
-        rc = upload_into(d, b, d->staged, sh, sh.host_checked, src, false);
-        if (rc) return rc;
-        t_up = std::chrono::steady_clock::now();
-        rc = dev_search(d, d->staged, &none, RES_CTX, true, 0, st, &enq);
-        if (rc) return drained(d, rc);
-    }
-    const auto t_search = std::chrono::steady_clock::now();
-    rc = gather_node(c, d, block);
-    if (rc) return drained(d, rc);
-    // the records land in pinned memory (a copy into the caller's pageable
-    // array would be a synchronous staged copy) and are copied out after the wait
-    if (d->node_n > d->hnode_cap) {
-        if (d->hnode) (void)hipHostFree(d->hnode);
-        d->hnode = nullptr;
-        d->hnode_cap = 0;
-        if (hipHostMalloc((void **)&d->hnode, (size_t)d->node_n * 8, hipHostMallocDefault) != hipSuccess)
-            return drained(d, lc::fail(LC_E_NOMEM, "lc_check_node: pinned record buffer"));
-        d->hnode_cap = d->node_n;
-    }
-    if (d->node_n && hipMemcpyAsync(d->hnode, d->node, (size_t)d->node_n * 8, hipMemcpyDeviceToHost, d->stream) !=
-                         hipSuccess)
-        return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node: record download failed"));
-    const auto t_gather = std::chrono::steady_clock::now();
-    if (enq) {  // a T0-only step (or chunks): one wait for the search, the exchange and the download
-        int n_async = 0;
-        float span = 0;
-        rc = dev_wait(d, &n_async, &span);
-        if (rc) return drained(d, rc);
-        if (st) st->kernel_ms = st->tier0_ms = span;
-    } else {
-        HIPCHK(hipStreamSynchronize(d->stream));
-    }
-    if (d->node_n) std::memcpy(node, d->hnode, (size_t)d->node_n * 8);
-    if (std::getenv("LC_TIMING")) {
-        using ms = std::chrono::duration<double, std::milli>;
-        std::fprintf(stderr, "lc_check_node: prepare %.3f, upload %.3f, search enqueue %.3f, gather enqueue %.3f, "
-                     "wait %.3f ms (search span %.3f)\n", ms(t_prep - t0).count(), ms(t_up - t_prep).count(),
-                     ms(t_search - t_up).count(), ms(t_gather - t_search).count(),
-                     ms(std::chrono::steady_clock::now() - t_gather).count(), st ? st->kernel_ms : 0.f);
-    }
-    if (st) st->total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return LC_OK;
-}
-
 // What dev_search will plan for a node step whose results stay in the
 // context (plan_lane decides from it before the search is enqueued).
-static lc::StepPlan node_step_plan(Dev *c, const DevBatch *d) {
+lc::StepPlan lcx::node_step_plan(Dev *c, const DevBatch *d) {
     const Step s{c, d, nullptr, RES_CTX, d->n_keys, {}};
     return lc::plan_step(step_in(s, true));
-}
-
-// The pipelined form of lc_check_node.  A register-tier step (every key fits
-// the register lattice, no probe counting, one upload, records to page-locked
-// memory) is only enqueued: its upload goes into the staging slot the step
-// three back used (once that step is done) on the copy stream, its search
-// follows that upload on one of the two search lanes, and the records land
-// in `node` with the search or behind it.  So step i + 2's host-to-device
-// copy overlaps the searches of steps i and i + 1, step i + 1's workgroups
-// take the slots step i's finished blocks free (lane_plan.hpp), and the host
-// enqueues ahead instead of waiting between steps.
-// Anything else runs as lc_check_node.
-extern "C" int lc_check_node_async(lc_ctx *c, const lc_batch *b, int64_t block, uint64_t *node, lc_stats *st) {
-    lc::Range range("lc_check_node_async");
-    if (!c || !b || !node) return lc::fail(LC_E_INVALID, "lc_check_node_async: null argument");
-    Dev *d = nullptr;
-    Shape sh;
-    const uint32_t *src = nullptr;
-    {
-        std::lock_guard<std::mutex> g(c->mu);
-        int rc = node_check_args(c, b->n_keys, block);
-        if (rc) return rc;
-        d = c->dev[0];
-        HIPCHK(hipSetDevice(d->device));
-        const int64_t K = b->n_keys;
-        const uint64_t n_ev = K ? b->ev_off[K] : 0;
-        // (a large shard is not cut into chunks here: its whole upload
-        // overlaps the previous step's search instead)
-        if (K > 0 && n_ev > 0 && !b->table && !(c->o.flags & LC_OPT_COUNT_PROBES) && pinned(node) &&
-            !(c->o.path_flags & LC_PATH_NODE_SYNC)) {
-            rc = prepare_batch(c, b, &sh, &src);
-            if (rc) return rc;
-            if (sh.t0_only) {
-                // where the step runs is plan_lane's choice (lane_plan.hpp);
-                // its staging slot follows from the sequence number alone
-                lc::LaneIn li;
-                li.seq = d->pipe_next;
-                const int s = lc::plan_lane(li).slot;
-                if (!d->pipe[s]) {
-                    d->pipe[s] = new (std::nothrow) DevBatch();
-                    if (!d->pipe[s]) return lc::fail(LC_E_NOMEM, "lc_check_node_async: out of memory");
-                    // (a device-scope release: the host only learns from it
-                    // that the upload's device writes are done)
-                    if (hipEventCreateWithFlags(&d->pipe_ready[s], hipEventDisableTiming | hipEventReleaseToDevice) !=
-                        hipSuccess) {
-                        (void)hipGetLastError();
-                        HIPCHK(hipEventCreateWithFlags(&d->pipe_ready[s], hipEventDisableTiming));
-                    }
-                }
-                // the step that last read this slot (three back) has finished
-                // -- at most two other steps stay in flight, one on each lane
-                // -- so its buffers may be rewritten or regrown.  Its end is
-                // the ring event its search recorded: a marker of its own
-                // after every step cost the stream ~5 us between consecutive
-                // searches (a system-scope fence each).
-                // (A ring slot re-recorded since by a later step only makes
-                // this wait for that later step.)
-                if (d->pipe_busy[s]) HIPCHK(hipEventSynchronize(d->ring[d->pipe_seq[s] % 4]));
-                d->pipe_busy[s] = false;
-                rc = upload_into(d, b, d->pipe[s], sh, sh.host_checked, src, false, d->cstream);
-                if (rc) return drained(d, rc);
-                HIPCHK(hipEventRecord(d->pipe_ready[s], d->cstream));
-                // The lane, and how the records reach `node`.  One rank: the
-                // search writes them straight into the caller's page-locked
-                // buffer (device-mapped), so no download follows it -- unless
-                // a step still in flight was given that buffer too and this
-                // step may overlap it: then they go through the lane's block
-                // in HBM and are copied out behind that step's end, so the
-                // buffer ends up with the latest step's records.  With a
-                // communicator they go through HBM for the all-gather.
-                uint64_t *dnode = nullptr;
-                li.mapped = hipHostGetDevicePointer((void **)&dnode, node, 0) == hipSuccess && dnode;
-                if (!li.mapped) (void)hipGetLastError();
-                const lc::StepPlan stp = node_step_plan(d, d->pipe[s]);
-                li.run_n = d->run_n;
-                li.async = stp.async; li.spec = stp.spec; li.split = stp.split;
-                li.waves = K * stp.segs;
-                li.resident_waves = (int64_t)d->cu_count * 4 * LC_SPEC8_WAVES;
-                li.comm = c->comm != nullptr;
-                li.path_flags = c->o.path_flags;
-                li.lo = (uint64_t)(uintptr_t)node;
-                li.hi = li.lo + (uint64_t)std::max<int64_t>(block, 1) * 8;
-                for (int t = 0; t < Dev::PIPE; ++t) {
-                    if (t == s || !d->pipe_busy[t]) continue;
-                    if (hipEventQuery(d->ring[d->pipe_seq[t] % 4]) == hipSuccess) {
-                        d->pipe_busy[t] = false;
-                        continue;
-                    }
-                    (void)hipGetLastError();
-                    lc::LaneIn::Flight &f = li.flight[li.n_flight++];
-                    f.seq = d->pipe_seq[t]; f.lo = d->pipe_lo[t]; f.hi = d->pipe_hi[t];
-                }
-                const lc::LanePlan lp = lc::plan_lane(li);
-                LaneUse lu;
-                lu.lane = lp.lane;
-                lu.overlap = lp.overlap;
-                if (lp.direct) {
-                    if (block > K) std::memset(node + K, 0, (size_t)(block - K) * 8);
-                    d->rec_out = dnode;
-                } else if (lp.overlap) {
-                    rc = lane_records(d, d->lane[lp.lane], K, block);
-                    if (rc) return drained(d, rc);
-                    lu.dst = node;
-                    lu.n = (size_t)block;
-                    lu.after = lp.after >= 0 ? d->ring[lp.after % 4] : nullptr;
-                } else {
-                    rc = node_buffers(c, d, K, block);
-                    if (rc) return drained(d, rc);
-                }
-                RecOff rec_off{d};
-                // The host waits for the upload (the steps before are
-                // searching meanwhile) and then enqueues the search: no
-                // cross-stream wait on the device, whose latency sat between
-                // consecutive searches (C2 0.3415 -> 0.3365 ms per step).  It
-                // also frees the context's staging copy of pageable events.
-                HIPCHK(hipEventSynchronize(d->pipe_ready[s]));
-                lc_result none{};
-                bool enq = false;
-                rc = dev_search(d, d->pipe[s], &none, RES_CTX, true, 0, st, &enq, 0, &lu);
-                if (rc) return drained(d, rc);
-                if (lp.direct || lu.dst) {
-                    d->node_n = 0;  // the records are in `node` only (lc_node_records has none)
-                } else {
-                    rc = gather_node(c, d, block);
-                    if (rc) return drained(d, rc);
-                    if (d->node_n && hipMemcpyAsync(node, d->node, (size_t)d->node_n * 8, hipMemcpyDeviceToHost,
-                                                    d->stream) != hipSuccess)
-                        return drained(d, lc::fail(LC_E_DEVICE, "lc_check_node_async: record download failed"));
-                }
-                d->pipe_busy[s] = enq;
-                d->pipe_seq[s] = d->async_seq - 1;
-                d->pipe_lo[s] = li.lo;
-                d->pipe_hi[s] = li.hi;
-                ++d->pipe_next;
-                if (enq) return 1;
-                HIPCHK(hipStreamSynchronize(d->stream));  // not reached for a register-tier batch
-                return LC_OK;
-            }
-        }
-    }
-    return lc_check_node(c, b, block, node, st);
 }
 
 extern "C" void *lc_host_alloc(size_t bytes) {
@@ -2442,49 +1730,13 @@ extern "C" void lc_host_free(void *p) {
     if (p) (void)hipHostFree(p);
 }
 
-extern "C" int lc_check_node_device(lc_ctx *c, const lc_dev_batch *db, int64_t block, int flags, lc_stats *st) {
-    if (!c || !db) return lc::fail(LC_E_INVALID, "lc_check_node_device: null argument");
-    if (flags & ~LC_DEV_ASYNC) return lc::fail(LC_E_INVALID, "lc_check_node_device: unknown flags 0x%x", flags);
-    std::lock_guard<std::mutex> g(c->mu);
-    int rc = node_check_args(c, db->n_keys, block);
-    if (rc) return rc;
-    if (db->n_parts != 1 || db->part[0]->device != c->dev[0]->device)
-        return lc::fail(LC_E_INVALID, "lc_check_node_device: batch lives on another device");
-    Dev *d = c->dev[0];
-    lc_result none{};
-    bool enq = false;
-    rc = node_buffers(c, d, db->n_keys, block);
-    if (rc) return rc;
-    rc = dev_search(d, db->part[0], &none, RES_CTX, (flags & LC_DEV_ASYNC) != 0, 0, st, &enq);
-    if (rc) { d->rec_out = nullptr; return rc; }
-    rc = gather_node(c, d, block);
-    if (rc) return rc;
-    if (!enq) HIPCHK(hipStreamSynchronize(d->stream));
-    return LC_OK;
-}
-
-extern "C" int lc_node_records(lc_ctx *c, uint64_t *node, int64_t n) {
-    if (!c || (!node && n)) return lc::fail(LC_E_INVALID, "lc_node_records: null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    Dev *d = c->dev[0];
-    if (n > d->node_n) return lc::fail(LC_E_INVALID, "lc_node_records: %lld records asked, %lld gathered",
-                                       (long long)n, (long long)d->node_n);
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    if (n) HIPCHK(hipMemcpyAsync(node, d->node, (size_t)n * 8, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return LC_OK;
-}
-
 // ---- the set workload (set.clj:46; device_set.hip) ---------------------------
 
 extern "C" int lc_set_check(lc_ctx *c, const lc_set_batch *b, lc_set_result *r) {
     if (!c || !b || !r) return lc::fail(LC_E_INVALID, "lc_set_check: null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    Dev *d = c->dev[0];
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    return lcs::set_check(&d->setdev, d->stream, c->o.path_flags, b, r);
+    CtxCall x(c);
+    LCCHK(x.enter());
+    return lcs::set_check(&x.d->setdev, x.d->stream, c->o.path_flags, b, r);
 }
 
 extern "C" int lc_set_last_timing(lc_ctx *c, double *out_ms) {
@@ -2497,348 +1749,13 @@ extern "C" int lc_set_last_timing(lc_ctx *c, double *out_ms) {
 
 extern "C" int lc_perf_check(lc_ctx *c, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r) {
     if (!c || !b || !o || !r) return lc::fail(LC_E_INVALID, "lc_perf_check: null argument");
-    std::lock_guard<std::mutex> g(c->mu);
-    Dev *d = c->dev[0];
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    return lcp::perf_check(&d->perfdev, d->stream, b, o, r);
+    CtxCall x(c);
+    LCCHK(x.enter());
+    return lcp::perf_check(&x.d->perfdev, x.d->stream, b, o, r);
 }
 
 extern "C" int lc_perf_last_timing(lc_ctx *c, double *out_ms) {
     if (!c || !out_ms) return lc::fail(LC_E_INVALID, "lc_perf_last_timing: null argument");
     std::lock_guard<std::mutex> g(c->mu);
     return lcp::perf_last_timing(c->dev[0]->perfdev, out_ms);
-}
-
-// ---- a resident search (lc_stream_*; device_lattice.hip k_stream) ---------------
-// host_stream.cpp owns the stream (its packer, verdicts and C entry points);
-// this is its device half: the per-key records and one launch per call.
-
-static_assert(sizeof(lcst::Item) == sizeof(lcd::StreamItem) && offsetof(lcst::Item, ns) == offsetof(lcd::StreamItem, ns),
-              "lcst::Item is lcd::StreamItem");
-
-struct lcst::StreamDev {
-    lc_ctx *ctx = nullptr;
-    uint32_t *rec = nullptr;   // STREAM_REC_WORDS per key
-    int64_t rec_cap = 0;       // keys
-    char *din = nullptr, *hin = nullptr;  // a call's items, transitions, words: device, pinned host
-    size_t in_cap = 0;
-    uint32_t *dout = nullptr, *hout = nullptr;  // the dead list
-    size_t out_cap = 0;        // words
-    hipEvent_t ev[6] = {};     // [4], [5]: after the migrations, after k_stream_set
-    float ms[3] = {0, 0, 0};
-    // the resident set tier: the set-record pool -- chunk c holds
-    // SET_CHUNK0 << c slots of stream_set_slot_bytes() and never moves -- and
-    // k_stream_set's workspace, one slot per resident workgroup
-    std::vector<uint32_t *> set_chunk;
-    std::vector<int32_t> set_free;
-    int64_t set_slots = 0, set_used = 0, set_peak = 0;
-    char *set_ws = nullptr;
-    int set_ws_slots = 0;
-    float set_ms[2] = {0, 0};
-};
-
-namespace {
-constexpr size_t STREAM_OUT_HEAD = 63;  // dead keys read back with the count, in one copy
-constexpr int64_t SET_CHUNK0 = 4;       // slots of the set-record pool's first chunk
-constexpr int SET_GRID = 64;            // k_stream_set workgroups (and workspace slots) at most
-size_t up16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// Pool slot -> its record (chunk c starts at slot SET_CHUNK0 * (2^c - 1)).
-uint32_t *set_slot_ptr(const lcst::StreamDev *s, int64_t slot) {
-    if (slot < 0 || slot >= s->set_slots) return nullptr;
-    int c = 0;
-    int64_t first = 0;
-    while (slot >= first + (SET_CHUNK0 << c)) first += SET_CHUNK0 << c++;
-    return s->set_chunk[(size_t)c] + (size_t)(slot - first) * lc::STREAM_SET_REC_WORDS;
-}
-
-// k_stream_set's workspace for `slots` resident workgroups, hash sets empty.
-int set_ws_grow(lcst::StreamDev *s, Dev *d, int slots) {
-    if (slots <= s->set_ws_slots) return LC_OK;
-    const lcd::StreamSetWs w = lcd::stream_set_ws_layout();
-    const int want = std::min(SET_GRID, std::max(slots, 2 * s->set_ws_slots));
-    if (s->set_ws) (void)hipFree(s->set_ws);
-    s->set_ws = nullptr;
-    s->set_ws_slots = 0;
-    HIPCHK(hipMalloc((void **)&s->set_ws, (size_t)want * w.slot_bytes));
-    HIPCHK(hipMemsetAsync(s->set_ws, 0xFF, (size_t)want * w.slot_bytes, d->stream));  // EMPTY tables
-    s->set_ws_slots = want;
-    return LC_OK;
-}
-
-int stream_grow(lcst::StreamDev *s, Dev *d, int64_t n_keys, size_t in_bytes, size_t out_words) {
-    if (n_keys > s->rec_cap) {
-        const int64_t cap = std::max<int64_t>({n_keys, 2 * s->rec_cap, 64});
-        uint32_t *nr = nullptr;
-        HIPCHK(dalloc(&nr, (size_t)cap * lc::STREAM_REC_WORDS));
-        const size_t old = (size_t)s->rec_cap * lc::STREAM_REC_WORDS * 4, all = (size_t)cap * lc::STREAM_REC_WORDS * 4;
-        hipError_t e = hipSuccess;
-        if (old) e = hipMemcpyAsync(nr, s->rec, old, hipMemcpyDeviceToDevice, d->stream);
-        if (e == hipSuccess) e = hipMemsetAsync((char *)nr + old, 0, all - old, d->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
-        if (e != hipSuccess) {
-            dfree(nr);
-            return lc::fail(LC_E_DEVICE, "lc_stream: growing the records failed: %s", hipGetErrorString(e));
-        }
-        dfree(s->rec);
-        s->rec = nr;
-        s->rec_cap = cap;
-    }
-    if (in_bytes > s->in_cap) {
-        const size_t cap = std::max<size_t>(in_bytes * 2, 1 << 16);
-        if (s->din) (void)hipFree(s->din);
-        if (s->hin) (void)hipHostFree(s->hin);
-        s->din = s->hin = nullptr;
-        s->in_cap = 0;
-        HIPCHK(hipMalloc((void **)&s->din, cap));
-        HIPCHK(hipHostMalloc((void **)&s->hin, cap, hipHostMallocDefault));
-        s->in_cap = cap;
-    }
-    if (out_words > s->out_cap) {
-        const size_t cap = std::max<size_t>(out_words * 2, 1024);
-        dfree(s->dout);
-        if (s->hout) (void)hipHostFree(s->hout);
-        s->hout = nullptr;
-        s->out_cap = 0;
-        HIPCHK(dalloc(&s->dout, cap));
-        HIPCHK(hipHostMalloc((void **)&s->hout, cap * 4, hipHostMallocDefault));
-        s->out_cap = cap;
-    }
-    return LC_OK;
-}
-}  // namespace
-
-int lcst::stream_dev_open(lc_ctx *c, StreamDev **out) {
-    if (c->n_dev != 1 || c->comm)
-        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: a stream needs a context of one device and no communicator");
-    if (c->o.max_configs < lc::STREAM_MIN_BUDGET)
-        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: budget %llu is below %llu, where the register tier's sets are exact",
-                        (unsigned long long)c->o.max_configs, (unsigned long long)lc::STREAM_MIN_BUDGET);
-    std::lock_guard<std::mutex> g(c->mu);
-    HIPCHK(hipSetDevice(c->dev[0]->device));
-    StreamDev *s = new StreamDev;
-    s->ctx = c;
-    for (hipEvent_t &e : s->ev) {
-        hipError_t r = hipEventCreate(&e);
-        if (r != hipSuccess) {
-            for (hipEvent_t &x : s->ev)
-                if (x) (void)hipEventDestroy(x);
-            delete s;
-            return lc::fail(LC_E_DEVICE, "lc_stream_open: hipEventCreate failed: %s", hipGetErrorString(r));
-        }
-    }
-    *out = s;
-    return LC_OK;
-}
-
-void lcst::stream_dev_close(StreamDev *s) {
-    if (!s) return;
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    Dev *d = s->ctx->dev[0];
-    (void)hipSetDevice(d->device);
-    (void)hipStreamSynchronize(d->stream);
-    dfree(s->rec);
-    dfree(s->dout);
-    for (uint32_t *&c : s->set_chunk) dfree(c);
-    if (s->set_ws) (void)hipFree(s->set_ws);
-    if (s->din) (void)hipFree(s->din);
-    if (s->hin) (void)hipHostFree(s->hin);
-    if (s->hout) (void)hipHostFree(s->hout);
-    for (hipEvent_t e : s->ev)
-        if (e) (void)hipEventDestroy(e);
-    delete s;
-}
-
-void lcst::stream_dev_timing(const StreamDev *s, double *out3) {
-    for (int i = 0; i < 3; ++i) out3[i] = s->ms[i];
-}
-
-int lcst::stream_dev_set_alloc(StreamDev *s, int32_t *slot) {
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    if (s->set_free.empty()) {
-        if (s->set_slots > ((int64_t)1 << 20)) return lc::fail(LC_E_DEVICE, "lc_stream: the set-record pool is full");
-        HIPCHK(hipSetDevice(s->ctx->dev[0]->device));
-        const int64_t n = SET_CHUNK0 << s->set_chunk.size();
-        uint32_t *c = nullptr;
-        HIPCHK(dalloc(&c, (size_t)n * lc::STREAM_SET_REC_WORDS));
-        s->set_chunk.push_back(c);
-        for (int64_t i = n; i-- > 0;) s->set_free.push_back((int32_t)(s->set_slots + i));
-        s->set_slots += n;
-    }
-    *slot = s->set_free.back();
-    s->set_free.pop_back();
-    s->set_peak = std::max(s->set_peak, ++s->set_used);
-    return LC_OK;
-}
-
-void lcst::stream_dev_set_free(StreamDev *s, int32_t slot) {
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    if (slot < 0 || slot >= s->set_slots) return;
-    s->set_free.push_back(slot);
-    --s->set_used;
-}
-
-void lcst::stream_dev_set_stats(const StreamDev *s, double *out6) {
-    out6[0] = s->set_ms[0];
-    out6[1] = s->set_ms[1];
-    out6[2] = (double)s->set_slots;
-    out6[3] = (double)s->set_used;
-    out6[4] = (double)s->set_peak;
-    out6[5] = (double)lc::stream_set_slot_bytes();
-}
-
-int lcst::stream_dev_set_record(StreamDev *s, int32_t slot, int64_t off, uint32_t *out, int64_t words) {
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    const uint32_t *p = set_slot_ptr(s, slot);
-    if (!p || off < 0 || words < 0 || off + words > (int64_t)lc::STREAM_SET_REC_WORDS)
-        return lc::fail(LC_E_INVALID, "lc_stream_set_record: no such record");
-    if (!words) return LC_OK;
-    Dev *d = s->ctx->dev[0];
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    HIPCHK(hipMemcpyAsync(out, p + off, (size_t)words * 4, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return LC_OK;
-}
-
-int lcst::stream_dev_record(StreamDev *s, int64_t key, uint32_t *out) {
-    std::lock_guard<std::mutex> g(s->ctx->mu);
-    if (key < 0 || key >= s->rec_cap) return lc::fail(LC_E_INVALID, "lc_stream_record: key %lld has no record", (long long)key);
-    Dev *d = s->ctx->dev[0];
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    HIPCHK(hipMemcpyAsync(out, s->rec + (size_t)key * lc::STREAM_REC_WORDS, lc::STREAM_REC_WORDS * 4, hipMemcpyDeviceToHost,
-                          d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    return LC_OK;
-}
-
-int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
-                          uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
-                          std::vector<Dead> *dead, const SetWork *set) {
-    dead->clear();
-    s->ms[0] = s->ms[1] = s->ms[2] = 0;
-    s->set_ms[0] = s->set_ms[1] = 0;
-    const int64_t n_mig = set ? set->n_mig : 0, n_set = set ? set->n_items : 0;
-    const uint64_t n_ev32 = set ? set->n_ev32 : 0;
-    if (n_items <= 0 && n_mig <= 0 && n_set <= 0) return LC_OK;
-    if (n_items < 0) n_items = 0;
-    if (n_items > (int64_t)1 << 30 || n_ev > 0xFFFFFFFFull || n_trans > 0xFFFFFFFFull || n_mig > (int64_t)1 << 24 ||
-        n_set > (int64_t)1 << 24 || n_ev32 > 0x3FFFFFFFull)
-        return lc::fail(LC_E_INVALID, "lc_stream: too much for one call");
-    for (int64_t i = 0; i < n_mig; ++i) {
-        const SetMig &m = set->mig[i];
-        if (m.key < 0 || m.key >= n_keys || !set_slot_ptr(s, m.slot))
-            return lc::fail(LC_E_INVALID, "lc_stream: migration %lld is out of range (internal error)", (long long)i);
-    }
-    for (int64_t i = 0; i < n_set; ++i) {
-        const SetItem &it = set->items[i];
-        if (it.key < 0 || it.key >= n_keys || !set_slot_ptr(s, it.slot) || it.ev_b > it.ev_e || it.ev_e > n_ev32 ||
-            it.tr_b > n_trans || it.ntr > n_trans - it.tr_b)
-            return lc::fail(LC_E_INVALID, "lc_stream: set work item %lld is out of range (internal error)", (long long)i);
-    }
-    // every index a wave follows, checked before the launch
-    for (int64_t i = 0; i < n_items; ++i) {
-        const Item &it = items[i];
-        if (it.key < 0 || it.key >= n_keys || it.ev_b > it.ev_e || it.ev_e > n_ev || it.tr_b > n_trans ||
-            it.ntr > n_trans - it.tr_b)
-            return lc::fail(LC_E_INVALID, "lc_stream: work item %lld is out of range (internal error)", (long long)i);
-    }
-    lc_ctx *c = s->ctx;
-    std::lock_guard<std::mutex> g(c->mu);
-    Dev *d = c->dev[0];
-    HIPCHK(hipSetDevice(d->device));
-    LCCHK(join_lanes(d));
-    const bool sets = n_mig > 0 || n_set > 0;
-    const size_t o_items = 0, o_trans = up16((size_t)n_items * sizeof(Item)),
-                 o_ev = o_trans + up16((size_t)n_trans * 4), o_mig = o_ev + up16((size_t)n_ev * 2),
-                 o_desc = o_mig + up16((size_t)n_mig * sizeof(lcd::StreamMigItem)),
-                 o_set = o_desc + up16((size_t)n_mig * 64 * 4),
-                 o_ev32 = o_set + up16((size_t)n_set * sizeof(lcd::StreamSetItem)),
-                 in_bytes = o_ev32 + up16((size_t)n_ev32 * 4);
-    // the set tier's list follows k_stream's
-    const size_t o_out2 = 1 + 4 * (size_t)n_items, out_words = o_out2 + (sets ? 1 + 4 * (size_t)n_set : 0);
-    LCCHK(stream_grow(s, d, n_keys, in_bytes, out_words));
-    if (n_set) LCCHK(set_ws_grow(s, d, (int)std::min<int64_t>(n_set, SET_GRID)));
-    if (n_items) std::memcpy(s->hin + o_items, items, (size_t)n_items * sizeof(Item));
-    if (n_trans) std::memcpy(s->hin + o_trans, trans, (size_t)n_trans * 4);
-    if (n_ev) std::memcpy(s->hin + o_ev, ev16, (size_t)n_ev * 2);
-    for (int64_t i = 0; i < n_mig; ++i) {
-        lcd::StreamMigItem m{set_slot_ptr(s, set->mig[i].slot), set->mig[i].key, (uint32_t)i * 64u};
-        std::memcpy(s->hin + o_mig + (size_t)i * sizeof m, &m, sizeof m);
-        std::memcpy(s->hin + o_desc + (size_t)i * 64 * 4, set->mig[i].descs, 64 * 4);
-    }
-    for (int64_t i = 0; i < n_set; ++i) {
-        const SetItem &it = set->items[i];
-        lcd::StreamSetItem m{set_slot_ptr(s, it.slot), it.key, it.ev_b, it.ev_e, it.tr_b, it.ntr, 0u};
-        std::memcpy(s->hin + o_set + (size_t)i * sizeof m, &m, sizeof m);
-    }
-    if (n_ev32) std::memcpy(s->hin + o_ev32, set->ev32, (size_t)n_ev32 * 4);
-    HIPCHK(hipEventRecord(s->ev[0], d->stream));
-    HIPCHK(hipMemcpyAsync(s->din, s->hin, in_bytes, hipMemcpyHostToDevice, d->stream));
-    HIPCHK(hipMemsetAsync(s->dout, 0, 4, d->stream));
-    if (sets) HIPCHK(hipMemsetAsync(s->dout + o_out2, 0, 4, d->stream));
-    HIPCHK(hipEventRecord(s->ev[1], d->stream));
-    lcd::StreamArgs a{};
-    a.items = (const lcd::StreamItem *)(s->din + o_items);
-    a.trans = (const uint32_t *)(s->din + o_trans);
-    a.events16 = (const uint16_t *)(s->din + o_ev);
-    a.rec = s->rec;
-    a.out = s->dout;
-    a.n_items = (int32_t)n_items;
-    a.init_state = init_state;
-    if (n_items) HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(n_items, 8192), d->stream));
-    HIPCHK(hipEventRecord(s->ev[2], d->stream));
-    if (sets) {
-        // in this order on the one lane: a key's register words, its migration,
-        // its set words -- each launch sees what the one before it stored
-        lcd::StreamSetArgs sa{};
-        sa.mig = (const lcd::StreamMigItem *)(s->din + o_mig);
-        sa.descs = (const uint32_t *)(s->din + o_desc);
-        sa.rec = s->rec;
-        sa.items = (const lcd::StreamSetItem *)(s->din + o_set);
-        sa.events32 = (const uint32_t *)(s->din + o_ev32);
-        sa.trans = a.trans;
-        sa.ws = lcd::stream_set_ws_layout();
-        sa.ws.base = s->set_ws;
-        sa.out = s->dout + o_out2;
-        sa.n_mig = (int32_t)n_mig;
-        sa.n_items = (int32_t)n_set;
-        sa.init_state = init_state;
-        if (n_mig) HIPCHK(lcd::launch_stream_migrate(sa, (int)std::min<int64_t>(n_mig, 8192), d->stream));
-        HIPCHK(hipEventRecord(s->ev[4], d->stream));
-        if (n_set) HIPCHK(lcd::launch_stream_set(sa, (int)std::min<int64_t>(n_set, s->set_ws_slots), d->stream));
-        HIPCHK(hipEventRecord(s->ev[5], d->stream));
-    }
-    const size_t head = sets ? out_words : std::min<size_t>(out_words, 1 + 4 * STREAM_OUT_HEAD);
-    HIPCHK(hipMemcpyAsync(s->hout, s->dout, head * 4, hipMemcpyDeviceToHost, d->stream));
-    HIPCHK(hipEventRecord(s->ev[3], d->stream));
-    HIPCHK(hipStreamSynchronize(d->stream));
-    const size_t n_dead = s->hout[0];
-    if (n_dead > (size_t)n_items) return lc::fail(LC_E_DEVICE, "lc_stream: the dead list holds more keys than the launch had");
-    if (1 + 4 * n_dead > head) {
-        HIPCHK(hipMemcpyAsync(s->hout + head, s->dout + head, (1 + 4 * n_dead - head) * 4, hipMemcpyDeviceToHost, d->stream));
-        HIPCHK(hipStreamSynchronize(d->stream));
-    }
-    const size_t n_left = sets ? s->hout[o_out2] : 0;
-    if (n_left > (size_t)n_set) return lc::fail(LC_E_DEVICE, "lc_stream: the set tier's list holds more keys than the launch had");
-    (void)hipEventElapsedTime(&s->ms[0], s->ev[0], s->ev[1]);
-    (void)hipEventElapsedTime(&s->ms[1], s->ev[1], s->ev[2]);
-    (void)hipEventElapsedTime(&s->ms[2], s->ev[sets ? 5 : 2], s->ev[3]);
-    if (sets) {
-        (void)hipEventElapsedTime(&s->set_ms[0], s->ev[2], s->ev[4]);
-        (void)hipEventElapsedTime(&s->set_ms[1], s->ev[4], s->ev[5]);
-    }
-    dead->resize(n_dead + n_left);
-    for (size_t i = 0; i < n_dead; ++i) {
-        const uint32_t *o = s->hout + 1 + 4 * i;
-        (*dead)[i] = Dead{o[0], o[1], o[2], o[3]};
-    }
-    for (size_t i = 0; i < n_left; ++i) {
-        const uint32_t *o = s->hout + o_out2 + 1 + 4 * i;
-        (*dead)[n_dead + i] = Dead{o[0], o[1], o[2], o[3]};
-    }
-    std::sort(dead->begin(), dead->end(), [](const Dead &x, const Dead &y) { return x.key < y.key; });
-    return LC_OK;
 }

@@ -1,5 +1,6 @@
 // device_perf.hpp -- checker/perf's analysis on the device (device_perf.hip):
-// what device_api.hip needs to run lc_perf_check on a context's stream.
+// what device_api.hip needs to run lc_perf_check on a context's stream (the
+// context keeps a PerfDev per device: device_ctx.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // Kernel argument block and launchers shared by device_search.hip and the
-// host orchestration in device_api.hip.
+// host orchestration in device_api.hip, device_node.hip and device_stream.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>

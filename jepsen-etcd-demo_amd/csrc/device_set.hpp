@@ -1,5 +1,6 @@
 // device_set.hpp -- the set-workload check on the device (device_set.hip):
-// what device_api.hip needs to run lc_set_check on a context's stream.
+// what device_api.hip needs to run lc_set_check on a context's stream (the
+// context keeps a SetDev per device: device_ctx.hpp).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // device_stream.hpp -- the device half of a stream (lc_stream_*): what
-// host_stream.cpp needs from device_api.hip to keep per-key search records
+// host_stream.cpp needs from device_stream.hip to keep per-key search records
 // resident and to advance them.  No HIP types here.
 #pragma once
 

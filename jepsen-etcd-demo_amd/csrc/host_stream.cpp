@@ -1,7 +1,7 @@
 // host_stream.cpp -- lc_stream_*: the streaming packer and the stream's
 // verdict book-keeping (include/lincheck.h "incremental check"; DESIGN.md
 // section 3.11).  The device half -- the per-key records and k_stream's
-// launch -- is device_api.hip's (device_stream.hpp).
+// launch -- is device_stream.hip's (device_stream.hpp).
 //
 // The packer restates lc_pack's steps (host_pack.cpp: pairing, complete's
 // value fill, without-failures, window slots, interning) for rows that arrive

@@ -1,4 +1,4 @@
-// Where an enqueued node step (lc_check_node_async, device_api.hip) runs: its
+// Where an enqueued node step (lc_check_node_async, device_node.hip) runs: its
 // search lane, whether it may overlap the step before it, how its records
 // reach the caller's buffer, and its staging slot -- as a pure function of
 // plain values, tested without a GPU (tests/test_lane_plan.py).  No HIP here.

@@ -1,6 +1,8 @@
 // Which kernels one search step runs: every rule of dev_search
 // (device_api.hip) as a pure function of plain values, so the choice is
 // tested as a choice, without a GPU (tests/test_step_plan.py).  No HIP here.
+// (device_node.hip asks for a node step's plan ahead of its search through
+// node_step_plan, device_ctx.hpp.)
 #pragma once
 
 #include <algorithm>

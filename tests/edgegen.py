@@ -35,10 +35,10 @@ SPEC_MIN_LEN = 128            # device_lattice.hip:1708 SPEC_MIN_LEN (events per
 SPEC_MAX_PEND = 6             # device_lattice.hip:1709 SPEC_MAX_PEND (ops pending at a cut at most)
 SPEC_CUT_WINDOW = 64          # device_lattice.hip:1846-1863 spec_cut_at (boundaries t .. t + 64)
 SPEC_EV_LDS = (3072, 4096)    # device_lattice.hip:2325 spec_ev_lds() (event words staged in LDS)
-SPEC_CK_DEFAULT = (32, 120)   # device_api.hip:1450-1451 (default checkpoint distances past a cut)
+SPEC_CK_DEFAULT = (32, 120)   # device_api.hip spec_launch (default checkpoint distances past a cut)
 T0_MAX_WIDTH = 10             # device_lattice.hip:62 LC_T0_MAX_WIDTH
 T0_MAX_STATES = 32            # device_lattice.hip:65 T0_MAX_STATES
-TAGGABLE_MAX_STATES = 6       # device_api.hip:817 (taggable: shared table, states 0..5)
+TAGGABLE_MAX_STATES = 6       # device_api.hip batch_shape (taggable: shared table, states 0..5)
 
 
 def spec_eff(nev: int, S: int) -> int:
@@ -477,7 +477,7 @@ def pending_before(pk: Packed, i: int) -> np.ndarray:
 
 def batch_states(pk: Packed) -> np.ndarray:
     """States per key as the register tier counts them: 1 + the largest state
-    id of a shared table (device_api.hip:805-811), else lc_batch.key_states."""
+    id of a shared table (device_api.hip batch_shape), else lc_batch.key_states."""
     from lincheck import _native as N
     if pk.view.trans_off:
         return N.carray(pk.view.key_states, pk.n_keys, np.uint16).astype(np.int64)

@@ -152,6 +152,65 @@ def test_errors_name_their_own_step_with_three_in_flight(cases):
     assert dev.wait()[0] == 1
 
 
+def _empty_batch():
+    keep = np.zeros(1, np.uint64)  # ev_off of no keys
+    b = N.LcBatch()
+    b.n_keys = 0
+    b.ev_off = N.ptr(keep, C.c_uint64)
+    return keep, b
+
+
+@pytest.fixture(scope="module")
+def small_steps():
+    """Three steps of 8 keys x 40 ops, one key invalid in each, and their
+    lc_check_node records on a fresh context."""
+    steps = []
+    for seed in (60, 63, 64):
+        pk = Packed(H.synth(n_keys=8, ops_per_key=40, concurrency=5, anomaly_rate=0.15, seed=seed))
+        ref = Device(0).check_node(pk, pk.n_keys + PAD)[0].copy()
+        assert (P.unpack_records(ref.astype(np.int64))[0][:pk.n_keys] == 0).sum() == 1
+        steps.append((pk, ref))
+    return steps
+
+
+# (what, Device arguments, page-locked buffers, one buffer for all steps, no keys, the return code)
+EXITS = [
+    ("pageable", {}, False, False, False, 0),
+    ("direct", {}, True, False, False, 1),
+    ("lane_block", {}, True, True, False, 1),
+    ("node_sync", dict(path_flags=N.LC_PATH_NODE_SYNC), True, False, False, 0),
+    ("count_probes", dict(count_probes=True), True, False, False, 0),
+    ("no_keys", {}, True, False, True, 0),
+]
+
+
+@pytest.mark.parametrize("what,kw,page_locked,shared,no_keys,want_rc", EXITS, ids=[e[0] for e in EXITS])
+def test_every_exit_of_the_enqueue_path(small_steps, what, kw, page_locked, shared, no_keys, want_rc):
+    """Every way out of lc_check_node_async, three steps back to back: it
+    returns 1 where the step is enqueued and 0 where it ran as lc_check_node
+    (a pageable buffer, LC_PATH_NODE_SYNC, probe counting, no keys), and the
+    node's bytes are lc_check_node's either way, padding zeroed."""
+    dev = Device(0, **kw)
+    block = 8 + PAD
+    make = PinnedRecords if page_locked else (lambda n: np.zeros(n, np.uint64))
+    one = make(block)
+    bufs = [one if shared else make(block) for _ in small_steps]
+    keep = []
+    for (pk, _), buf in zip(small_steps, bufs):
+        buf[:] = 0xDEAD
+        keep.append(_empty_batch() if no_keys else (pk, pk.view))
+        rc = N.check(N.lib().lc_check_node_async(dev.handle, C.byref(keep[-1][1]), block, N.ptr(buf, C.c_uint64), None))
+        assert rc == want_rc
+    assert dev.wait()[0] == (3 if want_rc else 0)
+    if no_keys:
+        fresh, empty = Device(0), np.full(block, 0xDEAD, np.uint64)
+        N.check(N.lib().lc_check_node(fresh.handle, C.byref(keep[0][1]), block, N.ptr(empty, C.c_uint64), None))
+    for i, ((_, ref), buf) in enumerate(zip(small_steps, bufs)):
+        want = empty if no_keys else small_steps[-1][1] if shared else ref
+        assert not want[0 if no_keys else 8:].any()
+        np.testing.assert_array_equal(np.asarray(buf), want, err_msg=f"{what}: step {i}")
+
+
 def test_synchronous_calls_behind_enqueued_steps(cases):
     """lc_check_batch and lc_check_node right behind three enqueued steps,
     no wait between: both see a context whose lanes they have joined and give
