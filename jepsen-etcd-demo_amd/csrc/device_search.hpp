@@ -70,7 +70,7 @@ constexpr int32_t LC_BATCH_E_FIT = 4;    // a key declared to fit T0 (width, sta
 // Ops pending at once above which a key leaving T0 goes straight to T3.
 constexpr uint32_t LC_DIRECT_T3_WIDTH = 28;
 
-// The speculative segments' 8-wave build (k_spec<8>, device_lattice.hip)
+// The speculative segments' 8-wave build (k_spec<8>, device_spec.hip)
 // held to 8 waves per SIMD -- 64 VGPRs, the rest spilled -- so a batch of up
 // to 1,024 keys (C2, C5) has all 8 walks of every key resident at once: the
 // launch chooses 8 segments per key there instead of 4 (round 5, C2
@@ -99,7 +99,7 @@ size_t lat_ws_words();
 // tiers read the err words first and do nothing over a malformed batch)
 hipError_t launch_validate(const Args &a, hipStream_t s, bool general);
 
-// A resident search (lc_stream_*, device_lattice.hip k_stream): one wave per
+// A resident search (lc_stream_*, device_stream_lattice.hip k_stream): one wave per
 // work item resumes a key's register-tier walk from its state record
 // (stream_plan.hpp), searches the item's new event words and stores the
 // record back.  All arrays are device pointers.
@@ -166,7 +166,7 @@ struct StreamSetArgs {
 hipError_t launch_stream_migrate(const StreamSetArgs &a, int grid, hipStream_t s);
 hipError_t launch_stream_set(const StreamSetArgs &a, int grid, hipStream_t s);
 
-// Key segments (device_lattice.hip, "Key segments"): a register-tier step
+// Key segments (device_segments.hip): a register-tier step
 // whose keys are cut at quiescent points and searched as independent
 // segments, then composed per key.  Device arrays of seg_cap entries each
 // (seg_cap = n_keys * max_seg), sized by the host.
@@ -197,7 +197,7 @@ struct SegArgs {
 };
 constexpr uint32_t SEG_MAX = 256;  // work items are key << 8 | segment
 hipError_t launch_segments(const SegArgs &a, int grid, hipStream_t s);
-// Speculative key segments (device_lattice.hip): keys order[0 .. n_order) of
+// Speculative key segments (device_spec.hip): keys order[0 .. n_order) of
 // a verdicts-only register-tier step, each a workgroup of `segs` waves (2, 3,
 // 4, 6, 8) searching segments from the full set and checking them against
 // each other, then a launch for the keys left to the unsegmented search;

@@ -1,4 +1,4 @@
-// device_stream.hip -- a resident search (lc_stream_*; device_lattice.hip
+// device_stream.hip -- a resident search (lc_stream_*; device_stream_lattice.hip
 // k_stream, device_stream_set.hip): the device half of a stream, behind
 // device_stream.hpp.  host_stream.cpp owns the stream (its packer, verdicts and
 // C entry points); this is the per-key records and the launches of one call.

@@ -2,7 +2,7 @@
 // LC_STREAM_SET_TIER).
 //
 // A key whose next invoke would leave the register tier (k_stream,
-// device_lattice.hip: 10 ops pending, 32 states) is not restarted at
+// device_stream_lattice.hip: 10 ops pending, 32 states) is not restarted at
 // lc_stream_finish: its lattice is written out once as a config set
 // (k_stream_migrate) and from then on each call searches the key's new words
 // from that set (k_stream_set), event by event as search_key_lds
@@ -88,7 +88,7 @@ __device__ __forceinline__ void set_report(const StreamSetArgs &a, int32_t key, 
 // ---- migration ---------------------------------------------------------------
 // Every set bit s of lattice word W[L] is the config (state s, ops L
 // linearized and pending); op indices become window slots as write_final_mem
-// (device_lattice.hip) translates them.  The lattice may be closed over the
+// (lattice_core.hpp) translates them.  The lattice may be closed over the
 // pending ops or, when the record is dirty, closed over all but the ops
 // invoked last: either is a set between S and its closure, which is all the
 // search needs.

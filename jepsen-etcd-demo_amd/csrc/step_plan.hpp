@@ -73,7 +73,7 @@ inline StepPlan plan_step(const StepIn &in) {
     p.t0_step = K > 0 && in.t0_only && !(in.flags & LC_OPT_COUNT_PROBES);
     // (competition: the WGL step needs the :linear step's causes)
     p.async = p.t0_step && in.allow_async && !p.competition && !in.res_host;
-    // Key segments (device_lattice.hip): verdicts only, a batch of about one
+    // Key segments (device_segments.hip): verdicts only, a batch of about one
     // key per SIMD or fewer (where each key's serial chain is exposed), and
     // quiescent points close enough for the cuts to pay (segments_pay: on
     // C2, whose clients think about as long as an op takes, the longest
@@ -82,7 +82,7 @@ inline StepPlan plan_step(const StepIn &in) {
     const bool fast = !in.want_peak && !in.want_final && in.max_configs >= 16ull * 64 * 32;
     const bool want = (in.path_flags & LC_PATH_SPLIT_ON) ? true : (in.path_flags & LC_PATH_SPLIT_OFF) ? false : in.seg_pays;
     p.split = p.t0_step && fast && in.taggable && want && K <= (int64_t)in.cu_count * 8;
-    // Speculative segments (device_lattice.hip): the same regime without
+    // Speculative segments (device_spec.hip): the same regime without
     // quiescent points -- every key a workgroup of `segs` waves, about four
     // segment waves per SIMD in all (C2: 1,000 keys x 4).  The kernel's 80
     // VGPRs would allow six, but 6-wave workgroups land unevenly on a CU's

@@ -1,5 +1,5 @@
 // A resident, resumable register-tier search (lc_stream_*):
-// the per-key state record k_stream (device_lattice.hip) loads and stores,
+// the per-key state record k_stream (device_stream_lattice.hip) loads and stores,
 // which of its words a load or a save touches, the phase a resumed walk
 // enters, and when a key leaves the stream for the batch path -- as pure
 // functions of plain values, tested without a GPU (tests/test_stream_plan.py).
@@ -37,7 +37,7 @@ constexpr uint32_t STREAM_REC_WORDS = STREAM_OFF_LATTICE + STREAM_LATTICE_MAX;
 
 constexpr uint32_t STREAM_LIVE = 0, STREAM_INVALID = 1, STREAM_ERROR = 2;
 
-// the register tier's reach (device_lattice.hip T0_MAX_WIDTH / T0_MAX_STATES)
+// the register tier's reach (lattice_core.hpp T0_MAX_WIDTH / T0_MAX_STATES)
 constexpr uint32_t STREAM_MAX_WIDTH = 10;
 constexpr uint32_t STREAM_MAX_STATES = 32;
 // the least budget at which the FAST walk's sets are exact: no lattice holds

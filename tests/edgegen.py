@@ -31,23 +31,23 @@ from lincheck import history as H
 from lincheck.checker import Packed
 from lincheck.independent import Tuple
 
-SPEC_MIN_LEN = 128            # device_lattice.hip:1708 SPEC_MIN_LEN (events per segment at least)
-SPEC_MAX_PEND = 6             # device_lattice.hip:1709 SPEC_MAX_PEND (ops pending at a cut at most)
-SPEC_CUT_WINDOW = 64          # device_lattice.hip:1846-1863 spec_cut_at (boundaries t .. t + 64)
-SPEC_EV_LDS = (3072, 4096)    # device_lattice.hip:2325 spec_ev_lds() (event words staged in LDS)
+SPEC_MIN_LEN = 128            # device_spec.hip SPEC_MIN_LEN (events per segment at least)
+SPEC_MAX_PEND = 6             # device_spec.hip SPEC_MAX_PEND (ops pending at a cut at most)
+SPEC_CUT_WINDOW = 64          # device_spec.hip spec_cut_at (boundaries t .. t + 64)
+SPEC_EV_LDS = (3072, 4096)    # device_spec.hip spec_ev_lds() (event words staged in LDS)
 SPEC_CK_DEFAULT = (32, 120)   # device_api.hip spec_launch (default checkpoint distances past a cut)
-T0_MAX_WIDTH = 10             # device_lattice.hip:62 LC_T0_MAX_WIDTH
-T0_MAX_STATES = 32            # device_lattice.hip:65 T0_MAX_STATES
+T0_MAX_WIDTH = 10             # lattice_core.hpp LC_T0_MAX_WIDTH
+T0_MAX_STATES = 32            # lattice_core.hpp T0_MAX_STATES
 TAGGABLE_MAX_STATES = 6       # device_api.hip batch_shape (taggable: shared table, states 0..5)
 
 
 def spec_eff(nev: int, S: int) -> int:
-    """Segments of a key of nev events on S waves (device_lattice.hip:2419-2420)."""
+    """Segments of a key of nev events on S waves (device_spec.hip k_spec, eff)."""
     return 1 if nev < 2 * SPEC_MIN_LEN else min(S, nev // SPEC_MIN_LEN)
 
 
 def spec_targets(nev: int, S: int) -> List[int]:
-    """Equal-count targets 1 .. eff - 1 (device_lattice.hip:2495)."""
+    """Equal-count targets 1 .. eff - 1 (device_spec.hip k_spec)."""
     eff = spec_eff(nev, S)
     return [nev * s // eff for s in range(1, eff)]
 
@@ -71,7 +71,7 @@ def spec_cut(c: Sequence[int], nev: int, t: int) -> Optional[int]:
 
 
 def spec_cuts(c: Sequence[int], nev: int, S: int) -> List[Optional[int]]:
-    """The kept cuts of segments 1 .. eff - 1 (device_lattice.hip:2524-2532):
+    """The kept cuts of segments 1 .. eff - 1 (device_spec.hip k_spec):
     a cut at or before the last kept one is dropped."""
     out, last = [], 0
     for t in spec_targets(nev, S):
@@ -84,11 +84,11 @@ def spec_cuts(c: Sequence[int], nev: int, S: int) -> List[Optional[int]]:
     return out
 
 
-SPEC_W_EV, SPEC_W_MID, SPEC_W_HEAVY = 8, 2, 240  # device_lattice.hip:1749 (an event, an :ok at 7-8, at 9-10 pending)
+SPEC_W_EV, SPEC_W_MID, SPEC_W_HEAVY = 8, 2, 240  # device_spec.hip SPEC_W_* (an event, an :ok at 7-8, at 9-10 pending)
 
 
 def spec_targets_cost(c: Sequence[int], nev: int, S: int) -> List[int]:
-    """LC_PATH_SPEC_COST's targets (device_lattice.hip:1784 spec_targets_cost):
+    """LC_PATH_SPEC_COST's targets (device_spec.hip spec_targets_cost):
     target s is the first event up to and including which the key has s / eff
     of its estimated cost."""
     eff = spec_eff(nev, S)

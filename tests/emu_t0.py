@@ -1,4 +1,4 @@
-"""Lane-level CPU model of the register-lattice tier (device_lattice.hip, T0).
+"""Lane-level CPU model of the register-lattice tier (lattice_core.hpp, T0).
 
 Test infrastructure: it re-executes the kernel's per-event steps on 64-lane
 numpy arrays -- the one-directional DPP / permlane gathers (with garbage on

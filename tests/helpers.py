@@ -1,11 +1,53 @@
-"""Shared test helpers: run the device and the oracle on the same history."""
+"""Shared test helpers: run the device and the oracle on the same history;
+read the built library's kernel metadata."""
+import os
+import re
+import subprocess
+
 import numpy as np
+import pytest
 
 import cref
 from lincheck import history as H
 from lincheck.checker import Device, Packed
 
 CAUSE = {"none": 0, "nonlin": 1, "budget": 2, "window": 3, "states": 4}
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SO = os.path.join(ROOT, "jepsen-etcd-demo_amd", "lincheck", "liblincheck.so")
+LLVM = "/opt/rocm/llvm/bin"
+
+
+def code_object_kernels(tmp_path):
+    """Kernel metadata (llvm-readelf --notes) of every source file's gfx950
+    code object: the library's .hip_fatbin section is one offload bundle per
+    .hip file, back to back."""
+    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
+        if not os.path.exists(os.path.join(LLVM, tool)):
+            pytest.skip(f"{tool} not in {LLVM}")
+    if not os.path.exists(SO):
+        pytest.skip("liblincheck.so not built")
+    fat = str(tmp_path / "fat.bin")
+    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", SO, str(tmp_path / "x")],
+                   check=True, capture_output=True)
+    data = open(fat, "rb").read()
+    magic = b"__CLANG_OFFLOAD_BUNDLE__"
+    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
+    out = {}
+    for i, b in enumerate(starts):
+        part, co = str(tmp_path / f"b{i}.bin"), str(tmp_path / f"k{i}.co")
+        open(part, "wb").write(data[b:starts[i + 1] if i + 1 < len(starts) else len(data)])
+        subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
+                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
+        notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
+                               text=True).stdout
+        for block in re.split(r"\n  - \.agpr_count:", notes):
+            m = re.search(r"\.name:\s+(\S+)", block)
+            if m:
+                out[m.group(1)] = {k: int(v) for k, v in re.findall(
+                    r"\.(vgpr_count|group_segment_fixed_size|private_segment_fixed_size|max_flat_workgroup_size):\s+(\d+)",
+                    block)}
+    return out
 
 
 def device_vs_oracle(hist: H.History, dev: Device, budget=None, check_peak=True, verdicts_only=False):

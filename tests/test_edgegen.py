@@ -43,16 +43,16 @@ def oks(b, name):
 
 # ---------------------------------------------------------------- the constants
 @pytest.mark.parametrize("file,pattern,value", [
-    ("device_lattice.hip", r"constexpr uint32_t SPEC_MIN_LEN = (\d+);", E.SPEC_MIN_LEN),
-    ("device_lattice.hip", r"constexpr uint32_t SPEC_MAX_PEND = (\d+);", E.SPEC_MAX_PEND),
-    ("device_lattice.hip", r"#define LC_T0_MAX_WIDTH (\d+)", E.T0_MAX_WIDTH),
-    ("device_lattice.hip", r"constexpr uint32_t T0_MAX_STATES = (\d+);", E.T0_MAX_STATES),
-    ("device_lattice.hip", r"spec_ev_lds\(\) \{ return .* \? (\d+)u : \d+u\) : 0u; \}", E.SPEC_EV_LDS[0]),
-    ("device_lattice.hip", r"spec_ev_lds\(\) \{ return .* \? \d+u : (\d+)u\) : 0u; \}", E.SPEC_EV_LDS[1]),
-    ("device_lattice.hip", r"SPEC_W_EV = (\d+), SPEC_W_MID = \d+, SPEC_W_HEAVY = \d+;", E.SPEC_W_EV),
-    ("device_lattice.hip", r"SPEC_W_EV = \d+, SPEC_W_MID = (\d+), SPEC_W_HEAVY = \d+;", E.SPEC_W_MID),
-    ("device_lattice.hip", r"SPEC_W_EV = \d+, SPEC_W_MID = \d+, SPEC_W_HEAVY = (\d+);", E.SPEC_W_HEAVY),
-    ("device_lattice.hip", r"of the boundaries t\s*\n?//\s*\.\. t \+ (\d+) ", E.SPEC_CUT_WINDOW),
+    ("device_spec.hip", r"constexpr uint32_t SPEC_MIN_LEN = (\d+);", E.SPEC_MIN_LEN),
+    ("device_spec.hip", r"constexpr uint32_t SPEC_MAX_PEND = (\d+);", E.SPEC_MAX_PEND),
+    ("lattice_core.hpp", r"#define LC_T0_MAX_WIDTH (\d+)", E.T0_MAX_WIDTH),
+    ("lattice_core.hpp", r"constexpr uint32_t T0_MAX_STATES = (\d+);", E.T0_MAX_STATES),
+    ("device_spec.hip", r"spec_ev_lds\(\) \{ return .* \? (\d+)u : \d+u\) : 0u; \}", E.SPEC_EV_LDS[0]),
+    ("device_spec.hip", r"spec_ev_lds\(\) \{ return .* \? \d+u : (\d+)u\) : 0u; \}", E.SPEC_EV_LDS[1]),
+    ("device_spec.hip", r"SPEC_W_EV = (\d+), SPEC_W_MID = \d+, SPEC_W_HEAVY = \d+;", E.SPEC_W_EV),
+    ("device_spec.hip", r"SPEC_W_EV = \d+, SPEC_W_MID = (\d+), SPEC_W_HEAVY = \d+;", E.SPEC_W_MID),
+    ("device_spec.hip", r"SPEC_W_EV = \d+, SPEC_W_MID = \d+, SPEC_W_HEAVY = (\d+);", E.SPEC_W_HEAVY),
+    ("device_spec.hip", r"of the boundaries t\s*\n?//\s*\.\. t \+ (\d+) ", E.SPEC_CUT_WINDOW),
     ("device_api.hip", r"l\.ck1 = o\.spec_ck \? .* : (\d+)u;", E.SPEC_CK_DEFAULT[0]),
     ("device_api.hip", r"l\.ck2 = o\.spec_ck \? .* : (\d+)u;", E.SPEC_CK_DEFAULT[1]),
     ("device_api.hip", r"s\.taggable = !b->trans_off && s\.shared_states <= (\d+) ", E.TAGGABLE_MAX_STATES),
@@ -67,7 +67,7 @@ def test_restated_constant(file, pattern, value):
 
 def test_restated_segment_rules():
     """eff, the equal-count targets and the cut window as the kernel states them."""
-    src = open(os.path.join(CSRC, "device_lattice.hip")).read()
+    src = open(os.path.join(CSRC, "device_spec.hip")).read()
     assert "nev < 2 * SPEC_MIN_LEN;" in src and "min((uint32_t)S, nev / SPEC_MIN_LEN)" in src
     assert "const uint32_t t = (uint32_t)((uint64_t)nev * s / eff);" in src
     assert "if (c2 >= 0 && c2 <= last) c2 = -1;" in src
@@ -245,7 +245,7 @@ def test_every_segment_has_heavy_oks(segs):
 def test_burst_drops_a_cut():
     """Equal-cost targets (LC_PATH_SPEC_COST, 4 segments) 2 and 3 lie in the
     burst of 9-10-pending :oks and find the same boundary right after it: the
-    second cut is at the last kept one and is dropped (device_lattice.hip:2529)."""
+    second cut is at the last kept one and is dropped (device_spec.hip k_spec)."""
     c = pending(E.get("profiles"), "burst_same_boundary-valid")
     t = E.spec_targets_cost(c, E.NEV, 4)
     assert len(t) == 3 and t[2] - t[1] < E.SPEC_CUT_WINDOW

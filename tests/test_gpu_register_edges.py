@@ -1,4 +1,5 @@
-"""The register tier (device_lattice.hip) on histories built to a schedule
+"""The register tier (lattice_core.hpp, device_lattice.hip, device_spec.hip) on
+histories built to a schedule
 (tests/edgegen.py): ragged batches with keys on both sides of every length
 threshold, chosen pending counts at the cut windows of the speculative
 segments, several waves in the 9-10-pending workspaces at once, failing :oks

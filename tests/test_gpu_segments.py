@@ -1,4 +1,4 @@
-"""Key segments (device_lattice.hip, "Key segments"): verdict-only
+"""Key segments (device_segments.hip): verdict-only
 register-tier steps over about one key per SIMD cut each key at quiescent
 points, search every segment from all start states at once (tagged lattice
 words) and compose per key; a key that dies is searched again, untagged, in

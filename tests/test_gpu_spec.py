@@ -1,4 +1,4 @@
-"""Speculative key segments (device_lattice.hip, "Speculative key segments"):
+"""Speculative key segments (device_spec.hip):
 verdict-only register-tier steps of about one key per SIMD or fewer search
 every key as a workgroup of segment waves -- each segment from the full
 config set, then again from its predecessor's end set until the two runs

@@ -1,5 +1,5 @@
 """The incremental check on the device (lc_stream_*: k_stream in
-device_lattice.hip, csrc/host_stream.cpp).  Expected values always come from
+device_stream_lattice.hip, csrc/host_stream.cpp).  Expected values always come from
 the oracle (oracle/linear_ref.c through cref) or from Device.check one-shot:
 a stream fed a history in pieces must end with the records of the one-shot
 check, and after every call the set of invalid keys must be exactly the keys

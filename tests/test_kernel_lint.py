@@ -1,6 +1,6 @@
 """Static checks on kernel source shapes that once hung a wave on the GPU.
 
-Round 3: a `for (;;) ... break` walk loop in k_spec (device_lattice.hip) was
+Round 3: a `for (;;) ... break` walk loop in k_spec (device_spec.hip) was
 compiled into an exec-masked loop whose exit hung the wave after its first
 walk; it was replaced by fixed trip counts over uni()-uniform values.  The
 kernel's LDS-flag waits (spec_wait, spec_ck_event) are loops of the same kind.
@@ -34,7 +34,7 @@ OPEN_LOOP = r"for\s*\(\s*;\s*;\s*\)|while\s*\(\s*(true|1)\s*\)"
 
 
 def test_spec_walks_and_flag_waits_keep_fixed_trip_counts():
-    src = _code(open(os.path.join(CSRC, "device_lattice.hip")).read())
+    src = _code(open(os.path.join(CSRC, "device_spec.hip")).read())
     head = re.search(r"__global__ __launch_bounds__\([^{;]*\) void k_spec\(", src)
     assert head, "k_spec's definition not found"
     k_spec = _body(src, head.group(0))

@@ -9,41 +9,12 @@ and their LDS lets 4 (8-wave) or 16 (2-wave) workgroups share a CU's 160 KB;
 an edit that grows either would lose the occupancy without any test on the
 GPU failing (only the time).  So the limits are checked here, in the kernel
 descriptors' metadata (llvm-readelf --notes of the offload bundle)."""
-import os
-import re
-import shutil
-import subprocess
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SO = os.path.join(ROOT, "jepsen-etcd-demo_amd", "lincheck", "liblincheck.so")
-LLVM = "/opt/rocm/llvm/bin"
+from helpers import LLVM, SO  # noqa: F401 (test_set_kernels, test_perf_kernels)
+from helpers import code_object_kernels as _kernels
+
 LDS_PER_CU = 160 * 1024
-
-
-def _kernels(tmp_path):
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
-        if not os.path.exists(os.path.join(LLVM, tool)):
-            pytest.skip(f"{tool} not in {LLVM}")
-    if not os.path.exists(SO):
-        pytest.skip("liblincheck.so not built")
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "k.co")
-    subprocess.run([os.path.join(LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", SO, str(tmp_path / "x")],
-                   check=True, capture_output=True)
-    subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={fat}",
-                    "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-    notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                           text=True).stdout
-    out = {}
-    for block in re.split(r"\n  - \.agpr_count:", notes):
-        m = re.search(r"\.name:\s+(\S+)", block)
-        if not m:
-            continue
-        f = {k: int(v) for k, v in re.findall(r"\.(vgpr_count|group_segment_fixed_size|private_segment_fixed_size"
-                                               r"|max_flat_workgroup_size):\s+(\d+)", block)}
-        out[m.group(1)] = f
-    return out
 
 
 def _waves_per_simd(k):

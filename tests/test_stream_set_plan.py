@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from helpers import code_object_kernels
 from lincheck import _native as N
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -69,45 +70,12 @@ def test_fallback_rule_at_its_edges(exe):
 
 
 # ---------------------------------------------------------------- the new kernels' code objects
-def _all_kernels(tmp_path):
-    """Kernel metadata of every source file's code object: the library's
-    .hip_fatbin section is one offload bundle per file, back to back
-    (test_occupancy._kernels reads the first, device_lattice.hip's)."""
-    import test_occupancy as O
-    for tool in ("llvm-objcopy", "clang-offload-bundler", "llvm-readelf"):
-        if not os.path.exists(os.path.join(O.LLVM, tool)):
-            pytest.skip(f"{tool} not in {O.LLVM}")
-    if not os.path.exists(O.SO):
-        pytest.skip("liblincheck.so not built")
-    fat = str(tmp_path / "fat.bin")
-    subprocess.run([os.path.join(O.LLVM, "llvm-objcopy"), f"--dump-section=.hip_fatbin={fat}", O.SO, str(tmp_path / "x")],
-                   check=True, capture_output=True)
-    data = open(fat, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    starts = [m.start() for m in re.finditer(re.escape(magic), data)]
-    out = {}
-    for i, b in enumerate(starts):
-        part, co = str(tmp_path / f"b{i}.bin"), str(tmp_path / f"k{i}.co")
-        open(part, "wb").write(data[b:starts[i + 1] if i + 1 < len(starts) else len(data)])
-        subprocess.run([os.path.join(O.LLVM, "clang-offload-bundler"), "--unbundle", "--type=o", f"--input={part}",
-                        "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"], check=True, capture_output=True)
-        notes = subprocess.run([os.path.join(O.LLVM, "llvm-readelf"), "--notes", co], check=True, capture_output=True,
-                               text=True).stdout
-        for block in re.split(r"\n  - \.agpr_count:", notes):
-            m = re.search(r"\.name:\s+(\S+)", block)
-            if m:
-                out[m.group(1)] = {k: int(v) for k, v in re.findall(
-                    r"\.(vgpr_count|group_segment_fixed_size|private_segment_fixed_size|max_flat_workgroup_size):\s+(\d+)",
-                    block)}
-    return out
-
-
 def test_set_tier_kernels_code_objects(tmp_path):
     """k_stream_migrate is one wave and keeps nothing in LDS; k_stream_set is a
     256-thread workgroup whose sets live in device memory: under 1 KB of LDS
     (descriptors, two candidate lists, counters) and at most 64 VGPRs, so
     neither bounds residency below 8 waves per SIMD.  No scratch in either."""
-    ks = _all_kernels(tmp_path)
+    ks = code_object_kernels(tmp_path)
     mig, st = "_ZN3lcd16k_stream_migrateENS_13StreamSetArgsE", "_ZN3lcd12k_stream_setENS_13StreamSetArgsE"
     assert mig in ks and st in ks, [k for k in ks if "stream" in k]
     for name in (mig, st):
