@@ -23,9 +23,12 @@ namespace lcd {
 //      and past cut + ck2 (checkpoints), its failing event if it dies, and its
 //      set at the segment's end;
 //   2. every wave s >= 1 then searches its segment again from the set segment
-//      s - 1 ended with, until the two runs meet at a checkpoint.  Inductively
-//      every set is then exact: where they meet, the TOP run IS the real run
-//      from there on, so its death (or survival) is the segment's;
+//      s - 1 ended with, until the two runs meet: at one of the first :oks,
+//      by set size alone (the TOP run's set contains the other's, so equal
+//      config counts are equal sets: spec_meet_word), else at a checkpoint.
+//      Inductively every set is then exact: where they meet, the TOP run IS
+//      the real run from there on, so its death (or survival) is the
+//      segment's;
 //   3. wave 0 walks the segments in order: the key fails in the first
 //      segment whose real run dies.  A pair of runs that never met (not seen
 //      on any measured history) sends the key to the unsegmented search.
@@ -250,6 +253,8 @@ __device__ __forceinline__ void spec_setup(SpecState &st, uint32_t words, uint32
 // (the register tier's FAST path).  MODE 0 (TOP run): records the set after
 // the first lane-phase :ok at or past b + ck1 and past b + ck2 into ck_w /
 // ck_e.  MODE 1 (verifying run): compares with them at those events.
+// `meet` (verdict builds, may be null): the segment's meeting entries, which
+// MODE 0 publishes and MODE 1 compares with before the first checkpoint.
 // Returns 0 alive at e_end (st: the walk's state there; st.W0 the lattice if
 // st.n <= 6), 1 dead at fev, 3 the key does not fit the register tier,
 // 4 (MODE 1) met the TOP run, 5 (MODE 1) passed both checkpoints unmet.
@@ -354,13 +359,56 @@ __device__ __forceinline__ int32_t spec_ck_event(const int32_t *ck_e, uint32_t i
     return -1;
 }
 
+// Meeting by set size (verdict builds).  Both runs of a segment use the same
+// op-index assignment and the TOP run starts from a superset, so after every
+// lane-phase :ok its closed set contains the verifying run's bit by bit, and
+// the two are equal exactly when their config counts are (DESIGN.md,
+// "Speculative key segments").  The TOP run publishes, for each of its first
+// SPEC_MEET_N successful :oks before its first checkpoint, one word: the :ok's
+// ordinal in the segment << 16 | the wave sum of popc(W0) (at most 2,048), or
+// SPEC_MEET_NOCMP for an :ok taken in the dense phase (so ordinals stay
+// aligned).  The verifying run computes the same word and has met the TOP run
+// where they are equal.  Past the ring, or where the TOP run ended without
+// the entry or the wait gave up, it goes on to the checkpoints.
+// A/B: make variant VFLAGS=-DLC_SPEC_MEET=0.
+#ifndef LC_SPEC_MEET
+#define LC_SPEC_MEET 1
+#endif
+// Closed sets at 7-10 ops pending as in the lane phase (ok_reg_closed,
+// ok_event_mem_closed), `dirty` carried across the phase switches.
+// A/B: make variant VFLAGS=-DLC_SPEC_CLOSED=0.
+#ifndef LC_SPEC_CLOSED
+#define LC_SPEC_CLOSED 1
+#endif
+constexpr uint32_t SPEC_MEET_N = 16;  // ck1 = 32 events hold about 16 :oks
+constexpr uint32_t SPEC_MEET_NOCMP = 0xFFFFu;
+__device__ __forceinline__ int32_t spec_meet_word(uint32_t ord, uint32_t W0) {
+    const uint32_t cnt = (uint32_t)__builtin_amdgcn_readlane(wave_scan((int32_t)__popc(W0)), 63);
+    return (int32_t)((ord << 16) | cnt);
+}
+// The TOP run's meeting entry i, as spec_ck_event waits for a checkpoint:
+// until that run has published it or has ended without it (-1; -1 on a
+// timeout too).
+__device__ __forceinline__ int32_t spec_meet_entry(const int32_t *mt, uint32_t i, const int32_t *top_done) {
+#pragma unroll 1
+    for (uint32_t it = 0; it < SPEC_WAIT_MAX; ++it) {
+        const int32_t v = spec_load(mt + i);
+        if (v >= 0) return v;
+        if (spec_load(top_done) != 0) return spec_load(mt + i);
+        __builtin_amdgcn_s_sleep(2);
+    }
+    return -1;
+}
+
 template <int MODE, int NWS, class EvT, bool EX = false>
 __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t ntr, uint32_t b,
                                          uint32_t e_end, SpecState &st, uint32_t *ws, uint32_t *lds_ws,
                                          int32_t *lds_busy, uint32_t (*ck_w)[64], int32_t *ck_e, uint32_t ck1,
                                          uint32_t ck2, uint32_t &fev_out, bool prio = false,
-                                         uint32_t *save = nullptr, const int32_t *top_done = nullptr) {
+                                         uint32_t *save = nullptr, const int32_t *top_done = nullptr,
+                                         int32_t *meet = nullptr) {
     constexpr int RM = T0_RSMALL;
+    constexpr bool MEETC = LC_SPEC_MEET && !EX, CLOSED = LC_SPEC_CLOSED && !EX;
     const uint32_t lane = lane_id();
     LatMem m{ws, ws + T0_RMEM * 64, ws + 2 * T0_RMEM * 64};
     int32_t held = -1;  // LDS slot held
@@ -413,6 +461,10 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
     }
     uint32_t W0 = st.W0;
     bool dirty = true;
+    // meeting entries (MEETC): the next :ok's ordinal; on while the ring lasts
+    // and no checkpoint has been recorded / compared
+    uint32_t mt_ord = 0;
+    auto mt_on = [&]() -> bool { return MEETC && meet != nullptr && mt_ord < SPEC_MEET_N && ck_i == 0; };
     // One lane-phase event (<= 6 pending); true: an :invoke with 6 pending,
     // for the dense phase.  CK: the event may be a checkpoint's :ok.  The
     // events before the next checkpoint run the body without that test, so
@@ -494,6 +546,16 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
                         if (ck_i == SPEC_NCK) status = 5;
                     }
                 }
+            } else if (CK && !r && mt_on()) {  // a meeting entry (before the first checkpoint)
+                const int32_t mine = spec_meet_word(mt_ord, W0);
+                if constexpr (MODE == 0) {
+                    spec_publish(&meet[mt_ord], mine);
+                    ++mt_ord;
+                } else {
+                    const int32_t theirs = spec_meet_entry(meet, mt_ord, top_done);
+                    if (theirs == mine) status = 4;
+                    mt_ord = theirs < 0 ? SPEC_MEET_N : mt_ord + 1u;
+                }
             }
         }
         lim = status ? 0u : lim;
@@ -503,7 +565,8 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
     for (uint32_t phase = 0; phase <= nev && e < lim; ++phase) {
         bool dense = false;
         while (e < lim) {  // lane phase: <= 6 pending
-            uint32_t stop = min(lim, ck_at);
+            // (while meeting entries are due, every event runs the CK body)
+            uint32_t stop = mt_on() ? e : min(lim, ck_at);
             while (e < stop) {
                 if (lane_event(std::false_type{})) { dense = true; break; }
                 stop = min(stop, lim);
@@ -545,15 +608,31 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
                     dense_v = setl(dense_v, slot, idx);
                     live |= 1u << idx;
                     ++n;
+                    dirty = true;
                 }
             } else {
                 const uint32_t p = __builtin_amdgcn_readlane(dense_v, slot & 63u);
                 uint32_t nSn = 0, probes = 0;
                 int r;
-                if (n == 7) r = ok_reg<2, RM>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false);
-                else if (n == 8) r = ok_reg<4, RM>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false);
-                else if (n == 9) r = ok_event_mem_gs<8>(m, p, n, k_v, cap_v, b_v, lane);
-                else r = ok_event_mem_gs<16>(m, p, n, k_v, cap_v, b_v, lane);
+                if constexpr (CLOSED) {
+                    if (n == 7) r = ok_reg_closed<2, RM>(W, p, k_v, cap_v, b_v, lane, dirty);
+                    else if (n == 8) r = ok_reg_closed<4, RM>(W, p, k_v, cap_v, b_v, lane, dirty);
+                    else if (n == 9) r = ok_event_mem_closed<8>(m, p, k_v, cap_v, b_v, lane, dirty);
+                    else r = ok_event_mem_closed<16>(m, p, k_v, cap_v, b_v, lane, dirty);
+                    dirty = false;
+                } else {
+                    if (n == 7) r = ok_reg<2, RM>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false);
+                    else if (n == 8) r = ok_reg<4, RM>(W, p, k_v, cap_v, b_v, lane, ~0ull, false, probes, nSn, false);
+                    else if (n == 9) r = ok_event_mem_gs<8>(m, p, n, k_v, cap_v, b_v, lane);
+                    else r = ok_event_mem_gs<16>(m, p, n, k_v, cap_v, b_v, lane);
+                }
+                if constexpr (MEETC) {
+                    if (!r && mt_on()) {  // no compare here: the ordinals stay aligned
+                        if constexpr (MODE == 0)
+                            spec_publish(&meet[mt_ord], (int32_t)((mt_ord << 16) | SPEC_MEET_NOCMP));
+                        ++mt_ord;
+                    }
+                }
                 const uint32_t last = n - 1;
                 const uint32_t s_last = __builtin_amdgcn_readlane(slot_v, last);
                 const uint32_t x0 = __builtin_amdgcn_readlane(k_v, last), x1 = __builtin_amdgcn_readlane(cap_v, last),
@@ -584,7 +663,8 @@ __device__ __forceinline__ int spec_walk(EvT evp, const uint32_t *trp, uint32_t 
             if (n <= 6) break;
         }
         W0 = W[0];
-        dirty = true;
+        // (closed dense sets: the set is as clean as the last event left it)
+        if constexpr (!CLOSED) dirty = true;
     }
     if constexpr (EX) {
         if (save) {
@@ -675,6 +755,8 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
     __shared__ int32_t s_cand[S], s_ncand[S];  // each target's cut (-1: none) and ops pending there
     __shared__ int32_t s_prdy[S], s_done[S];  // flags a verifying wave waits on: s_pend / s_top -3 of s out; TOP run of s ended
     __shared__ uint32_t s_vx[S][2];       // self-validation: each wave's part, XOR of its slots' one-hots
+    constexpr bool MEETC = LC_SPEC_MEET && !EX;
+    __shared__ int32_t s_meet[MEETC ? S : 1][SPEC_MEET_N];  // TOP run's meeting entries (-1: not published)
     constexpr int NWS = spec_lds_ws<S>();
     __shared__ uint32_t s_ws[NWS ? NWS * 3 * T0_RMEM * 64 : 1];  // 9-10-pending workspaces (12 KB each)
     __shared__ int32_t s_ws_busy[NWS ? NWS : 1];
@@ -742,6 +824,7 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
     const uint32_t topmask = nstates >= 32 ? ~0u : (1u << nstates) - 1u;
 
     if (threadIdx.x < NWS) s_ws_busy[threadIdx.x] = 0;
+    if (MEETC && threadIdx.x < S * SPEC_MEET_N) s_meet[threadIdx.x / SPEC_MEET_N][threadIdx.x % SPEC_MEET_N] = -1;
     __syncthreads();
     // T0_STRICT batches whose key the block staged whole: the key's
     // validation here, from LDS, its 64-event chunks split over the S waves
@@ -912,7 +995,8 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
             const int r = lost ? 6
                                : spec_walk<0, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
                                                                    s_ck[s], s_ck_e[s], KA.spec_ck1, KA.spec_ck2,
-                                                                   fev, !(KA.flags & T0_SPEC_NOPRIO), sv);
+                                                                   fev, !(KA.flags & T0_SPEC_NOPRIO), sv, nullptr,
+                                                                   (MEETC && s != 0) ? s_meet[s] : nullptr);
             s_end[s][lane] = st.W0;
             uint64_t map = 0;
             for (uint32_t q = 0; q < 6; ++q) {
@@ -957,7 +1041,7 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
                 // slower on C2 and most seeds, profiles/r06_segments_seeds.txt)
                 const int r = spec_walk<1, NWS, EvK, EX>(evp, trp, ntr, cut, end, st, ws, s_ws, s_ws_busy,
                                                                 s_ck[v], s_ck_e[v], 0, 0, fev, false, sv,
-                                                                &s_done[v]);
+                                                                &s_done[v], MEETC ? s_meet[v] : nullptr);
                 bool last = true;
                 for (uint32_t q = v + 1; q < eff; ++q) last = last && uni(s_cut[q]) < 0;
                 if (r == 4) ver = 1;                        // met the TOP run

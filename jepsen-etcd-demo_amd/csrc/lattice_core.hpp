@@ -706,6 +706,75 @@ __device__ __forceinline__ int ok_reg(uint32_t (&W)[RM], uint32_t p, uint32_t k_
     return 0;
 }
 
+// ok_reg on CLOSED sets (verdicts only; ok_lane_closed's identity at 7 or 8
+// ops pending): W is closed under every pending op when dirty (an op was
+// invoked since the last closure), the lanes / registers with bit p are kept
+// with that bit moved down, and `last` takes index p as in ok_reg.  A clean
+// :ok is the projection alone: no masks, no sweeps.
+// Returns 0 normal, 1 invalid (W then holds the closure).
+template <int RL, int RM>
+__device__ __forceinline__ int ok_reg_closed(uint32_t (&W)[RM], uint32_t p, uint32_t k_v, uint32_t cap_v,
+                                             uint32_t b_v, uint32_t lane, bool dirty) {
+    constexpr int NB = lat_bits<RL>();  // = ops pending
+    constexpr int NR = NB - 6;          // register bits
+    constexpr int rl = NR - 1;          // `last` = NB - 1 is register bit rl
+    if (dirty) {
+        LaneMasks m;
+        lane_masks<NB>(m, ~0u, k_v, cap_v, b_v, lane);  // (no op left out: p's steps belong to the closure)
+        uint32_t rk[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) rk[r] = __builtin_amdgcn_readlane(k_v, 6 + r);
+#pragma unroll 1
+        for (int s = 0; s < NB; ++s) {  // a path has at most NB steps
+            uint32_t nv[RL];
+#pragma unroll
+            for (int k = 0; k < RL; ++k) nv[k] = sweep_lanes<0, 6>(W[k], m);
+#pragma unroll
+            for (int r = 0; r < NR; ++r)
+#pragma unroll
+                for (int k = 0; k < RL; ++k)
+                    if ((k >> r) & 1) nv[k] = xacc(nv[k], nv[k ^ (1 << r)], rk[r], m.sc[6 + r], m.sb[6 + r]);
+            bool ch = false;
+#pragma unroll
+            for (int k = 0; k < RL; ++k) { ch |= nv[k] != W[k]; W[k] = nv[k]; }
+            if (!__any(ch)) break;
+        }
+    }
+    // the new set over indices 0 .. NB-2, index p now the op that was `last`:
+    // L with p comes from L + last, L without p from L + p (without last)
+    uint32_t Wn[RL];
+    uint32_t any = 0;
+    if (p == (uint32_t)(NB - 1)) {
+#pragma unroll
+        for (int k = 0; k < RL; ++k) Wn[k] = ((k >> rl) & 1) ? 0u : W[k | (1 << rl)];
+    } else if (p < 6) {
+        const uint32_t hp = (uint32_t)__builtin_amdgcn_sbfe((int)lane, (int)p, 1);  // lane bit p as 0 / ~0
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            if ((k >> rl) & 1) { Wn[k] = 0u; continue; }
+            const uint32_t u = gup_rt(W[k], p);
+            Wn[k] = (W[k | (1 << rl)] & hp) | (u & ~hp);
+        }
+    } else {
+        const uint32_t r = p - 6;
+#pragma unroll
+        for (int k = 0; k < RL; ++k) {
+            if ((k >> rl) & 1) { Wn[k] = 0u; continue; }
+            uint32_t src = W[k | (1 << rl)];
+#pragma unroll
+            for (int rr = 0; rr < rl; ++rr)
+                if (r == (uint32_t)rr && !((k >> rr) & 1)) src = W[k | (1 << rr)];
+            Wn[k] = src;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < RL; ++k) any |= Wn[k];
+    if (!__any(any != 0u)) return 1;
+#pragma unroll
+    for (int k = 0; k < RL; ++k) W[k] = Wn[k];
+    return 0;
+}
+
 // Lattice of a key with 9 or 10 ops pending: 16 x 64 words per array in the
 // block's LDS workspace, index k * 64 + lane.  Every lane reads and writes
 // only its own column (register-bit partners are in the same lane; lane-bit
@@ -870,6 +939,62 @@ __device__ __forceinline__ int ok_event_mem_gs(const LatMem &m, uint32_t p, uint
         const bool hl = (lane & llm) || ((uint32_t)k & lrm);
         mW[k * 64] = p == last ? r : (hl ? 0u : (hp ? src : r));
     }
+    return 0;
+}
+
+// ok_event_mem_gs on CLOSED sets (verdicts only; see ok_reg_closed): m.W is
+// closed in place when dirty, its part with bit p goes to m.R with that bit
+// moved down and `last` (a row bit: n >= 9) relocated to p, and back to m.W.
+// Returns 0 normal, 1 invalid (m.W then holds the closure).
+template <int RL>
+__device__ __forceinline__ int ok_event_mem_closed(const LatMem &m, uint32_t p, uint32_t k_v, uint32_t cap_v,
+                                                   uint32_t b_v, uint32_t lane, bool dirty) {
+    constexpr int NB = lat_bits<RL>();  // = ops pending (9 or 10)
+    constexpr int NR = NB - 6;
+    constexpr uint32_t lrm = 1u << (NR - 1);  // `last` = NB - 1 as a row bit
+    const uint32_t ol = opq_lane(lane);
+    uint32_t *const mW = m.W + ol, *const mR = m.R + ol;
+    if (dirty) {
+        LaneMasks lmk;
+        lane_masks<NB>(lmk, ~0u, k_v, cap_v, b_v, lane);
+        uint32_t rk[NR];
+#pragma unroll
+        for (int r = 0; r < NR; ++r) rk[r] = __builtin_amdgcn_readlane(k_v, 6 + r);
+#pragma unroll 1
+        for (int s = 0; s < NB; ++s) {
+            bool ch = false;
+#pragma unroll 1
+            for (int k = 0; k < RL; ++k) {
+                const uint32_t x = mW[k * 64];
+                uint32_t nv = sweep_lanes<0, 6>(x, lmk);
+#pragma unroll
+                for (int r = 0; r < NR; ++r)
+                    if ((k >> r) & 1) nv = xacc(nv, mW[(k ^ (1 << r)) * 64], rk[r], lmk.sc[6 + r], lmk.sb[6 + r]);
+                if (nv != x) {
+                    mW[k * 64] = nv;
+                    ch = true;
+                }
+            }
+            if (!__any(ch)) break;
+        }
+    }
+    const uint32_t plm = p < 6 ? 1u << p : 0u, prm = p >= 6 ? 1u << (p - 6) : 0u;
+    const bool p_last = p == (uint32_t)(NB - 1);
+    uint32_t cS = 0;
+#pragma unroll 1
+    for (int k = 0; k < RL; ++k) {
+        // L with p: from L + last, same lane; L without p: from L + p.  (The
+        // gather runs on every lane: no cross-lane op under a divergent mask.)
+        const uint32_t up = (uint32_t)__shfl_xor((int)mW[(k ^ prm) * 64], (int)plm);
+        const uint32_t wl = mW[(k | lrm) * 64];
+        const bool hp = (lane & plm) || ((uint32_t)k & prm);
+        const uint32_t r = ((uint32_t)k & lrm) ? 0u : (p_last || hp) ? wl : up;
+        mR[k * 64] = r;
+        cS |= r;
+    }
+    if (!__any(cS != 0u)) return 1;
+#pragma unroll 1
+    for (int k = 0; k < RL; ++k) mW[k * 64] = mR[k * 64];
     return 0;
 }
 
