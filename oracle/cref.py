@@ -37,6 +37,9 @@ def lib():
         L.oracle_wgl_check_history_model.restype = C.c_int64
         L.oracle_wgl_check_history_model.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+        L.oracle_key_sizes_model.restype = C.c_int64
+        L.oracle_key_sizes_model.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_int64, C.c_void_p, C.c_void_p,
+                                             C.c_int64, C.c_void_p]
         _lib = L
     return _lib
 
@@ -64,6 +67,34 @@ def check_history(hist_c, budget: int = 1 << 20, threads: int = 1, model: str = 
                    "itemsize": C.sizeof(OracleKeyResult)})
     arr = np.frombuffer(res, dtype=dt, count=nk).copy()
     return keys[:nk], arr
+
+
+def key_sizes(hist_c, key: int, budget: int = 1 << 20, model: str = "cas-register", result: bool = False):
+    """The :linear set sizes of one key at this budget (oracle_key_sizes_model):
+    (sizeI, sizeS), uint32 arrays indexed by event, one entry per event the
+    search walks (the deciding one included).  sizeI[e] is |I| after the
+    closure and sizeS[e] |S'| after apply of the :ok at event e; an :invoke
+    has 0 in both.  result=True: (sizeI, sizeS, the key's record) -- the record
+    check_history gives for the key."""
+    L = lib()
+    cap = max(int(hist_c.n), 1)
+    sizeI = np.zeros(cap, np.uint32)
+    sizeS = np.zeros(cap, np.uint32)
+    res = OracleKeyResult()
+    n = L.oracle_key_sizes_model(C.byref(hist_c), MODELS[model], budget, int(key), sizeI.ctypes.data,
+                                 sizeS.ctypes.data, cap, C.byref(res))
+    if n < 0:
+        raise RuntimeError(f"oracle_key_sizes failed: {n}")
+    if result:
+        return sizeI[:n].copy(), sizeS[:n].copy(), res
+    return sizeI[:n].copy(), sizeS[:n].copy()
+
+
+def need(hist_c, key: int, model: str = "cas-register") -> int:
+    """The least budget at which the :linear search decides the key:
+    max(max |I|, max |S'|) over the events the unbounded search walks."""
+    sizeI, sizeS = key_sizes(hist_c, key, budget=1 << 62, model=model)
+    return int(max(sizeI.max(initial=1), sizeS.max(initial=1)))
 
 
 def _result_dtype():

@@ -101,9 +101,19 @@ static inline cfg_t cfg_with_state(cfg_t c, uint32_t st) { c.hi = (c.hi & 0xFFFF
 /* ------------------------------------------------------------- the search */
 static inline int step(uint32_t s, desc_t d, uint32_t *out) { return kp_step(s, d, out); }
 
+/* What oracle_key_sizes_model asks check_key to record: |I| after the closure
+ * and |S'| after apply of every :ok walked, by event (an :invoke keeps 0). */
+typedef struct { uint32_t *sizeI, *sizeS; int64_t cap, walked; } size_rec;
+
+static inline void rec_size(size_rec *sr, uint32_t *a, int64_t ev, uint64_t n) {
+    if (!sr) return;
+    if (ev < sr->cap && a) a[ev] = (uint32_t)n;
+    if (ev + 1 > sr->walked) sr->walked = ev + 1;
+}
+
 /* Check one key: rows[] are its sub-history rows (history order). */
 static int check_key(const lc_history *h, const int64_t *rows, int64_t nr, uint64_t budget, int model,
-                     oracle_key_result *res) {
+                     oracle_key_result *res, size_rec *sr) {
     memset(res, 0, sizeof *res);
     res->valid = 1; res->fail_event = -1; res->peak = 1;
     kp_key kk;
@@ -138,6 +148,7 @@ static int check_key(const lc_history *h, const int64_t *rows, int64_t nr, uint6
             slot_of[id] = s;
             slot_desc[s] = desc[id];
             pend_slots[npend++] = s;
+            rec_size(sr, NULL, ev, 0);
             ev++;
             continue;
         }
@@ -168,11 +179,12 @@ static int check_key(const lc_history *h, const int64_t *rows, int64_t nr, uint6
                 int ins = cset_insert(&I, c2);
                 if (ins < 0) { rc = LC_E_NOMEM; break; }
                 if (ins == 1) {
-                    if (I.n > budget) { res->valid = -1; res->cause = LC_CAUSE_BUDGET; res->fail_event = (int32_t)ev; goto done; }
+                    if (I.n > budget) { rec_size(sr, sr ? sr->sizeI : NULL, ev, I.n); res->valid = -1; res->cause = LC_CAUSE_BUDGET; res->fail_event = (int32_t)ev; goto done; }
                     if (cvec_push(&list, c2)) { rc = LC_E_NOMEM; break; }
                 }
             }
         }
+        rec_size(sr, sr ? sr->sizeI : NULL, ev, I.n);
         for (uint64_t k = 0; rc == 0 && k < list.n; ++k) {
             cfg_t c = list.v[k];
             uint32_t s2;
@@ -181,6 +193,7 @@ static int check_key(const lc_history *h, const int64_t *rows, int64_t nr, uint6
             if (cset_insert(&Sn, cfg_with_state(c, s2)) < 0) rc = LC_E_NOMEM;
         }
         if (rc) break;
+        rec_size(sr, sr ? sr->sizeS : NULL, ev, Sn.n);
         if (Sn.n == 0) { res->valid = 0; res->cause = LC_CAUSE_NONLIN; res->fail_event = (int32_t)ev; break; }
         if (Sn.n > budget) { res->valid = -1; res->cause = LC_CAUSE_BUDGET; res->fail_event = (int32_t)ev; break; }
         { cset t = S; S = Sn; Sn = t; }
@@ -290,7 +303,7 @@ typedef struct {
 
 static int lin_key(void *ctx, int64_t k) {
     lin_job *j = (lin_job *)ctx;
-    int rc = check_key(j->h, j->rows + j->off[k], (int64_t)(j->off[k + 1] - j->off[k]), j->budget, j->model, &j->out[k]);
+    int rc = check_key(j->h, j->rows + j->off[k], (int64_t)(j->off[k + 1] - j->off[k]), j->budget, j->model, &j->out[k], NULL);
     if (rc == LC_E_INVALID || rc == LC_E_UNSUPPORTED) {  /* check-safe: this key alone */
         memset(&j->out[k], 0, sizeof j->out[k]);
         j->out[k].valid = -1; j->out[k].cause = LC_CAUSE_ERROR; j->out[k].fail_event = -1;
@@ -316,6 +329,37 @@ int64_t oracle_check_history_model(const lc_history *h, int model, uint64_t budg
     if (out_keys) memcpy(out_keys, keys, (size_t)nk * sizeof(int64_t));
     free(keys); free(off); free(rows);
     return rc ? rc : nk;
+}
+
+/*
+ * The set sizes of one key's search: the same check_key walk at this budget,
+ * with sizeI[e] = |I| after the closure and sizeS[e] = |S'| after apply of
+ * every :ok e it walks (an :invoke, and whatever the walk did not reach, stay
+ * 0; at an :ok the budget ends inside the closure sizeI is budget + 1 and
+ * sizeS 0).  Entries past `cap` are not written.  *res (may be NULL) gets the
+ * key's record.  Returns the number of events walked, the deciding one
+ * included, or a negative LC_E_* (LC_E_INVALID: no such key).
+ */
+int64_t oracle_key_sizes_model(const lc_history *h, int model, uint64_t budget, int64_t key,
+                               uint32_t *sizeI, uint32_t *sizeS, int64_t cap, oracle_key_result *res) {
+    int64_t *keys, *rows;
+    uint64_t *off;
+    int64_t nk = oracle_split_keys(h, &keys, &off, &rows);
+    if (nk < 0) return nk;
+    int64_t k = 0;
+    while (k < nk && keys[k] != key) ++k;
+    int64_t out = LC_E_INVALID;
+    if (k < nk) {
+        if (sizeI) memset(sizeI, 0, (size_t)cap * sizeof(uint32_t));
+        if (sizeS) memset(sizeS, 0, (size_t)cap * sizeof(uint32_t));
+        size_rec sr = {sizeI, sizeS, cap, 0};
+        oracle_key_result r;
+        int rc = check_key(h, rows + off[k], (int64_t)(off[k + 1] - off[k]), budget ? budget : (1ull << 20), model, &r, &sr);
+        if (res) *res = r;
+        out = rc ? rc : sr.walked;
+    }
+    free(keys); free(off); free(rows);
+    return out;
 }
 
 /* The demo's model, (model/cas-register) (etcdemo.clj:117). */

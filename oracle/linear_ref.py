@@ -297,6 +297,8 @@ class Analysis:
     probes: int = 0
     ops: List[Op] = field(default_factory=list)
     events: list = field(default_factory=list)
+    size_I: Dict[int, int] = field(default_factory=dict)  # event -> |I| after the closure (at the budget: budget + 1)
+    size_S: Dict[int, int] = field(default_factory=dict)  # event -> |S'| after apply
 
 
 def analysis(history: Sequence[dict], budget: int = DEFAULT_BUDGET,
@@ -355,17 +357,20 @@ def analysis(history: Sequence[dict], budget: int = DEFAULT_BUDGET,
                     if c not in I:
                         I.add(c)
                         if len(I) > budget:
+                            res.size_I[ei] = len(I)
                             res.valid, res.cause = "unknown", "budget"
                             res.fail_event, res.fail_pos = ei, pos
                             return res
                         nxt.append(c)
             frontier = nxt
+        res.size_I[ei] = len(I)
         for (st, L) in I:
             s2 = step(st, ops[p].f, ops[p].value)
             if s2 is INCONSISTENT:
                 continue
             res.probes += 1
             S_next.add((s2, L))
+        res.size_S[ei] = len(S_next)
         if not S_next:
             res.valid, res.cause = False, "nonlin"
             res.op_id, res.fail_event, res.fail_pos = p, ei, pos

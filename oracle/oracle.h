@@ -24,4 +24,9 @@ typedef int (*oracle_key_fn)(void *ctx, int64_t k);
 int64_t oracle_split_keys(const lc_history *h, int64_t **keys_out, uint64_t **off_out, int64_t **rows_out);
 int oracle_run_pool(int n_threads, int64_t nkeys, oracle_key_fn fn, void *ctx);
 
+/* :linear set sizes of one key, by event: |I| after the closure and |S'| after
+ * apply of every :ok the search walks at this budget (linear_ref.c). */
+int64_t oracle_key_sizes_model(const lc_history *h, int model, uint64_t budget, int64_t key,
+                               uint32_t *sizeI, uint32_t *sizeS, int64_t cap, oracle_key_result *res);
+
 #endif /* ORACLE_H */
