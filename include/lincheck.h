@@ -949,7 +949,31 @@ void lc_perf_hist_free(lc_perf_hist *h);
  * A stream is in one mode, fixed by its first call (mixing: LC_E_INVALID).  It
  * counts no probes and no peaks, and returns no final configs: to render the
  * counterexample of a key found invalid, run the ordinary checker on that
- * key's sub-history. */
+ * key's sub-history -- or open the stream with LC_STREAM_EXACT.
+ *
+ * Exact mode (LC_STREAM_EXACT in lc_stream_opts.flags; off by default, and
+ * without it nothing of the above changes).  The register tier's resident
+ * search then keeps Knossos's own config set per key, not a closed superset of
+ * it, so for any split of the history into calls:
+ *   - any lc_opts.max_configs is accepted.  A register-tier key becomes
+ *     LC_UNKNOWN / LC_CAUSE_BUDGET in the call whose searched prefix holds the
+ *     first event at which a set or a closure passes the budget; fail_event
+ *     names that event, the key is searched no further, and it is NOT on
+ *     lc_stream_update.invalid (lc_stream_results and lc_stream_key_tier --
+ *     LC_STREAM_TIER_DEAD -- show it);
+ *   - lc_stream_results also fills peak_configs, final_configs (max_final x 2
+ *     words per key) and n_final where the caller passes them.  A key that died
+ *     (invalid, or at the budget) has the set standing before the failing event
+ *     and the peak up to it, the words lc_check_batch writes for it; a live key
+ *     has its peak so far and n_final 0 until lc_stream_finish;
+ *   - after lc_stream_finish every key's valid, cause, fail_event, peak,
+ *     n_final and final_configs equal lc_pack + lc_check_batch on the
+ *     concatenated rows with the same context -- valid keys' end sets
+ *     included.  Deferred keys are checked at finish with peaks and final
+ *     configs requested;
+ *   - lc_stream_report renders a key's counterexample from the stream itself.
+ * LC_STREAM_EXACT with LC_STREAM_SET_TIER is refused (LC_E_UNSUPPORTED).
+ * LC_OPT_COUNT_PROBES on the context is ignored by a stream, as without it. */
 typedef struct lc_stream lc_stream;  /* library-owned */
 
 typedef struct lc_stream_update {
@@ -966,6 +990,8 @@ typedef struct lc_stream_update {
 
 /* Options of a stream beyond the packer's (additive to ABI 13). */
 #define LC_STREAM_SET_TIER 1u     /* keys past the register tier resume in the resident set tier */
+#define LC_STREAM_EXACT    2u     /* the register tier holds Knossos's exact sets: any budget,
+                                     peaks, final configs and counterexamples online (below) */
 typedef struct lc_stream_opts {
     uint32_t flags;               /* LC_STREAM_* bits; 0: as lc_stream_open */
 } lc_stream_opts;
@@ -981,8 +1007,9 @@ typedef struct lc_stream_opts {
 /* ctx NULL: a packer-only stream (rows mode without a device: the accessors
  * below work, lc_stream_results does not).  opts NULL: cas-register.  A
  * context of several devices or with a communicator, or one whose budget is
- * below 16 x 64 x 32 (where the register tier's sets are exact), is refused
- * with LC_E_UNSUPPORTED; so is LC_MODEL_MULTI_REGISTER.  The context must
+ * below 16 x 64 x 32 (where the register tier's sets are exact; any budget
+ * with LC_STREAM_EXACT), is refused with LC_E_UNSUPPORTED; so is
+ * LC_MODEL_MULTI_REGISTER.  The context must
  * outlive the stream. */
 int  lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream **out);
 /* The same with stream options (sopts NULL: none).  LC_STREAM_SET_TIER on a
@@ -995,8 +1022,21 @@ int  lc_stream_push(lc_stream *s, const lc_batch *chunk, const int64_t *key_ids,
 int  lc_stream_finish(lc_stream *s, lc_stream_update *u);
 /* valid, fail_event and cause of every key so far, in key-index order (the
  * other arrays of r are not touched).  Before lc_stream_finish a key that is
- * neither invalid nor in error is LC_VALID: nothing searched so far refutes it. */
+ * neither invalid nor in error is LC_VALID: nothing searched so far refutes it.
+ * An LC_STREAM_EXACT stream also fills r->peak_configs, r->final_configs
+ * ([n_keys * max_final * 2], unused words zero) and r->n_final where they are
+ * not NULL (see "Exact mode" above); analyzer is never touched. */
 int  lc_stream_results(lc_stream *s, lc_result *r);
+/* The words lc_report writes, for key i of a stream in rows mode: from the
+ * stream's own per-key event words, transitions, state values and event rows,
+ * so rows are positions in the concatenation of everything appended.  valid,
+ * fail_event, final_configs and n_final are the key's (lc_stream_results of an
+ * LC_STREAM_EXACT stream, or any other source of the same record).  Returns
+ * the word count and writes them when they fit cap.  Events mode has no rows:
+ * LC_E_UNSUPPORTED.  A packer-only stream can be asked too. */
+int64_t lc_stream_report(const lc_stream *s, int64_t i, int32_t valid, int32_t fail_event,
+                         const uint64_t *final_configs, uint32_t n_final, int32_t max_paths, int64_t *out,
+                         int64_t cap);
 /* Keys in order of first appearance; returns their count (out may be NULL). */
 int64_t lc_stream_keys(const lc_stream *s, int64_t *out);
 /* Key i's counts: out4 = events emitted (its decided prefix), rows held back,
@@ -1018,6 +1058,10 @@ const char *lc_stream_key_error(const lc_stream *s, int64_t i);
  * [3] readback (device events). */
 int  lc_stream_record(lc_stream *s, int64_t i, uint32_t *out);
 int  lc_stream_last_timing(const lc_stream *s, double *out_ms4);
+/* Diagnostics of an LC_STREAM_EXACT stream: out2 = device ms of
+ * lc_stream_finish's k_stream_final launch, and the live keys it wrote the end
+ * sets of (zeros before finish and without the flag). */
+int  lc_stream_exact_stats(const lc_stream *s, double *out2);
 /* Key i's tier (LC_STREAM_TIER_*; negative: an error code), and the count of
  * keys in each, out4[tier].  deferred_at (lc_stream_key_events) names the
  * event at which a key left the register tier, whatever became of it. */

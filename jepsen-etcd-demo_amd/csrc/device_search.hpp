@@ -123,6 +123,30 @@ struct StreamArgs {
 };
 hipError_t launch_stream(const StreamArgs &a, int grid, hipStream_t s);
 
+// The exact mode of a resident search (LC_STREAM_EXACT; device_stream_exact.hip):
+// k_stream_exact resumes the exact walk -- Knossos's own sets, their sizes
+// against `budget`, the running peak in the record's header -- over the same
+// items and records as k_stream, and a key that dies (STREAM_INVALID,
+// STREAM_BUDGET) leaves the set standing before the failing event in
+// final_cfg / n_final.  k_stream_final writes them for keys that are still
+// live (lc_stream_finish): keys[0 .. n_items) name the records.
+struct StreamExactArgs {
+    const StreamItem *items;  // k_stream_exact
+    const int32_t *keys;      // k_stream_final
+    const uint16_t *events16;
+    const uint32_t *trans;
+    uint32_t *rec;            // STREAM_REC_WORDS per key
+    uint32_t *out;            // as StreamArgs::out
+    uint64_t *final_cfg;      // [key][max_final][2] (stream_plan.hpp stream_final_off64)
+    uint32_t *n_final;        // [key]
+    uint64_t budget;
+    int32_t n_items;
+    uint32_t init_state;
+    int32_t max_final;
+};
+hipError_t launch_stream_exact(const StreamExactArgs &a, int grid, hipStream_t s);
+hipError_t launch_stream_final(const StreamExactArgs &a, int grid, hipStream_t s);
+
 // The resident set tier of a stream (device_stream_set.hip; the set record's
 // layout: stream_plan.hpp).  A migration item turns a key's register record
 // into a set record; a set item searches the key's new 32-bit event words from

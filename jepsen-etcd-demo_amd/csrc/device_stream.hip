@@ -35,6 +35,13 @@ struct lcst::StreamDev {
     char *set_ws = nullptr;
     int set_ws_slots = 0;
     float set_ms[2] = {0, 0};
+    // exact mode (LC_STREAM_EXACT): k_stream_exact's launches, and the keys'
+    // final configs and their counts beside the records (same capacity)
+    bool exact = false;
+    uint64_t *fin = nullptr;
+    uint32_t *nfin = nullptr;
+    hipEvent_t fev[2] = {};
+    float final_ms = 0;
 };
 
 namespace {
@@ -80,6 +87,32 @@ int stream_grow(StreamDev *s, Dev *d, int64_t n_keys, size_t in_bytes, size_t ou
         if (e != hipSuccess) {
             dfree(nr);
             return lc::fail(LC_E_DEVICE, "lc_stream: growing the records failed: %s", hipGetErrorString(e));
+        }
+        if (s->exact) {  // the final-config arrays grow with the records
+            const uint32_t mf = (uint32_t)s->ctx->o.max_final;
+            const size_t of = (size_t)lc::stream_final_bytes((uint64_t)s->rec_cap, mf);
+            const size_t af = (size_t)lc::stream_final_bytes((uint64_t)cap, mf);
+            const size_t on = (size_t)lc::stream_nfinal_bytes((uint64_t)s->rec_cap);
+            const size_t an = (size_t)lc::stream_nfinal_bytes((uint64_t)cap);
+            uint64_t *nf = nullptr;
+            uint32_t *nn = nullptr;
+            e = dalloc(&nf, af / 8);
+            if (e == hipSuccess) e = dalloc(&nn, an / 4);
+            if (e == hipSuccess && of) e = hipMemcpyAsync(nf, s->fin, of, hipMemcpyDeviceToDevice, d->stream);
+            if (e == hipSuccess && on) e = hipMemcpyAsync(nn, s->nfin, on, hipMemcpyDeviceToDevice, d->stream);
+            if (e == hipSuccess) e = hipMemsetAsync((char *)nf + of, 0, af - of, d->stream);
+            if (e == hipSuccess) e = hipMemsetAsync((char *)nn + on, 0, an - on, d->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(d->stream);
+            if (e != hipSuccess) {
+                dfree(nf);
+                dfree(nn);
+                dfree(nr);
+                return lc::fail(LC_E_DEVICE, "lc_stream: growing the final configs failed: %s", hipGetErrorString(e));
+            }
+            dfree(s->fin);
+            dfree(s->nfin);
+            s->fin = nf;
+            s->nfin = nn;
         }
         dfree(s->rec);
         s->rec = nr;
@@ -202,7 +235,23 @@ int push_enqueue(StreamDev *s, Dev *d, const Push &p, const PushLayout &l, size_
     HIPCHK(hipMemsetAsync(s->dout, 0, 4, d->stream));
     if (p.sets) HIPCHK(hipMemsetAsync(s->dout + l.out2, 0, 4, d->stream));
     HIPCHK(hipEventRecord(s->ev[1], d->stream));
-    if (p.n_items) HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(p.n_items, 8192), d->stream));
+    if (p.n_items && s->exact) {
+        lcd::StreamExactArgs xa{};
+        xa.items = a.items;
+        xa.events16 = a.events16;
+        xa.trans = a.trans;
+        xa.rec = s->rec;
+        xa.out = s->dout;
+        xa.final_cfg = s->fin;
+        xa.n_final = s->nfin;
+        xa.budget = s->ctx->o.max_configs;
+        xa.n_items = a.n_items;
+        xa.init_state = p.init_state;
+        xa.max_final = s->ctx->o.max_final;
+        HIPCHK(lcd::launch_stream_exact(xa, (int)std::min<int64_t>(p.n_items, 8192), d->stream));
+    } else if (p.n_items) {
+        HIPCHK(lcd::launch_stream(a, (int)std::min<int64_t>(p.n_items, 8192), d->stream));
+    }
     HIPCHK(hipEventRecord(s->ev[2], d->stream));
     // in this order on the one lane: a key's register words, its migration,
     // its set words -- each launch sees what the one before it stored
@@ -242,22 +291,50 @@ int push_read_lists(StreamDev *s, Dev *d, const Push &p, const PushLayout &l, si
     std::sort(dead->begin(), dead->end(), [](const Dead &x, const Dead &y) { return x.key < y.key; });
     return LC_OK;
 }
+
+// Exact mode: what the keys that died at an event left in the stream's arrays
+// and in their headers.  Few keys die in a call: three small copies each.
+int push_read_finals(StreamDev *s, Dev *d, int64_t n_keys, const std::vector<Dead> &dead, std::vector<Final> *fin) {
+    fin->assign(dead.size(), Final{});
+    const uint32_t mf = (uint32_t)s->ctx->o.max_final;
+    bool any = false;
+    for (size_t i = 0; i < dead.size(); ++i) {
+        const Dead &x = dead[i];
+        if ((x.status != lc::STREAM_INVALID && x.status != lc::STREAM_BUDGET) || (int64_t)x.key >= n_keys) continue;
+        Final &f = (*fin)[i];
+        HIPCHK(hipMemcpyAsync(f.cfg, s->fin + lc::stream_final_off64(x.key, mf, 0), lc::stream_final_words64(mf) * 8,
+                              hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(&f.n_final, s->nfin + x.key, 4, hipMemcpyDeviceToHost, d->stream));
+        HIPCHK(hipMemcpyAsync(&f.peak, s->rec + (size_t)x.key * lc::STREAM_REC_WORDS + lc::STREAM_H_PEAK, 4,
+                              hipMemcpyDeviceToHost, d->stream));
+        any = true;
+    }
+    if (any) HIPCHK(hipStreamSynchronize(d->stream));
+    for (Final &f : *fin) f.n_final = std::min(f.n_final, mf);
+    return LC_OK;
+}
 }  // namespace
 
-int lcst::stream_dev_open(lc_ctx *c, StreamDev **out) {
+int lcst::stream_dev_open(lc_ctx *c, bool exact, StreamDev **out) {
     if (c->n_dev != 1 || c->comm)
         return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: a stream needs a context of one device and no communicator");
-    if (c->o.max_configs < lc::STREAM_MIN_BUDGET)
+    if (exact && (c->o.max_final < 0 || c->o.max_final > (int32_t)lc::STREAM_MAX_FINAL))
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: max_final %d is past %u", c->o.max_final, lc::STREAM_MAX_FINAL);
+    if (!lc::stream_budget_ok(c->o.max_configs, exact))
         return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: budget %llu is below %llu, where the register tier's sets are exact",
                         (unsigned long long)c->o.max_configs, (unsigned long long)lc::STREAM_MIN_BUDGET);
     std::lock_guard<std::mutex> g(c->mu);
     HIPCHK(hipSetDevice(c->dev[0]->device));
     StreamDev *s = new StreamDev;
     s->ctx = c;
-    for (hipEvent_t &e : s->ev) {
-        hipError_t r = hipEventCreate(&e);
+    s->exact = exact;
+    hipEvent_t *const evs[] = {&s->ev[0], &s->ev[1], &s->ev[2], &s->ev[3], &s->ev[4], &s->ev[5], &s->fev[0], &s->fev[1]};
+    for (hipEvent_t *e : evs) {
+        hipError_t r = hipEventCreate(e);
         if (r != hipSuccess) {
             for (hipEvent_t &x : s->ev)
+                if (x) (void)hipEventDestroy(x);
+            for (hipEvent_t &x : s->fev)
                 if (x) (void)hipEventDestroy(x);
             delete s;
             return lc::fail(LC_E_DEVICE, "lc_stream_open: hipEventCreate failed: %s", hipGetErrorString(r));
@@ -274,6 +351,8 @@ void lcst::stream_dev_close(StreamDev *s) {
     (void)hipSetDevice(d->device);
     (void)hipStreamSynchronize(d->stream);
     dfree(s->rec);
+    dfree(s->fin);
+    dfree(s->nfin);
     dfree(s->dout);
     for (uint32_t *&c : s->set_chunk) dfree(c);
     if (s->set_ws) (void)hipFree(s->set_ws);
@@ -282,7 +361,62 @@ void lcst::stream_dev_close(StreamDev *s) {
     if (s->hout) (void)hipHostFree(s->hout);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : s->fev)
+        if (e) (void)hipEventDestroy(e);
     delete s;
+}
+
+int lcst::stream_dev_max_final(const StreamDev *s) { return s->ctx->o.max_final; }
+double lcst::stream_dev_final_ms(const StreamDev *s) { return s->final_ms; }
+
+int lcst::stream_dev_peaks(StreamDev *s, int64_t n_keys, uint32_t *out) {
+    if (!s->exact) return lc::fail(LC_E_INVALID, "lc_stream: peaks are kept in exact mode only");
+    CtxCall x(s->ctx);
+    LCCHK(x.enter());
+    const int64_t have = std::min(n_keys, s->rec_cap);  // keys past the records have searched nothing yet
+    if (have > 0) {
+        HIPCHK(hipMemcpy2DAsync(out, 4, s->rec + lc::STREAM_H_PEAK, (size_t)lc::STREAM_REC_WORDS * 4, 4, (size_t)have,
+                                hipMemcpyDeviceToHost, x.d->stream));
+        HIPCHK(hipStreamSynchronize(x.d->stream));
+    }
+    for (int64_t i = 0; i < n_keys; ++i) out[i] = i < have && out[i] ? out[i] : 1u;
+    return LC_OK;
+}
+
+int lcst::stream_dev_finals(StreamDev *s, int64_t n_keys, const int32_t *keys, int64_t n_live, uint32_t init_state,
+                            uint64_t *cfg, uint32_t *n_final) {
+    if (!s->exact) return lc::fail(LC_E_INVALID, "lc_stream: final configs are kept in exact mode only");
+    s->final_ms = 0;
+    if (n_keys <= 0) return LC_OK;
+    for (int64_t i = 0; i < n_live; ++i)
+        if (keys[i] < 0 || keys[i] >= n_keys)
+            return lc::fail(LC_E_INVALID, "lc_stream: live key %lld is out of range (internal error)", (long long)i);
+    CtxCall x(s->ctx);
+    LCCHK(x.enter());
+    LCCHK(stream_grow(s, x.d, n_keys, (size_t)n_live * 4, 0));
+    const uint32_t mf = (uint32_t)s->ctx->o.max_final;
+    if (n_live > 0) {
+        std::memcpy(s->hin, keys, (size_t)n_live * 4);
+        lcd::StreamExactArgs a{};
+        a.keys = (const int32_t *)s->din;
+        a.rec = s->rec;
+        a.final_cfg = s->fin;
+        a.n_final = s->nfin;
+        a.n_items = (int32_t)std::min<int64_t>(n_live, (int64_t)1 << 30);
+        a.init_state = init_state;
+        a.max_final = (int32_t)mf;
+        HIPCHK(hipMemcpyAsync(s->din, s->hin, (size_t)n_live * 4, hipMemcpyHostToDevice, x.d->stream));
+        HIPCHK(hipEventRecord(s->fev[0], x.d->stream));
+        HIPCHK(lcd::launch_stream_final(a, (int)std::min<int64_t>(n_live, 8192), x.d->stream));
+        HIPCHK(hipEventRecord(s->fev[1], x.d->stream));
+    }
+    const size_t bf = (size_t)lc::stream_final_bytes((uint64_t)n_keys, mf), bn = (size_t)lc::stream_nfinal_bytes((uint64_t)n_keys);
+    if (bf) HIPCHK(hipMemcpyAsync(cfg, s->fin, bf, hipMemcpyDeviceToHost, x.d->stream));
+    HIPCHK(hipMemcpyAsync(n_final, s->nfin, bn, hipMemcpyDeviceToHost, x.d->stream));
+    HIPCHK(hipStreamSynchronize(x.d->stream));
+    if (n_live > 0) (void)hipEventElapsedTime(&s->final_ms, s->fev[0], s->fev[1]);
+    for (int64_t i = 0; i < n_keys; ++i) n_final[i] = std::min(n_final[i], mf);
+    return LC_OK;
 }
 
 void lcst::stream_dev_timing(const StreamDev *s, double *out3) {
@@ -347,8 +481,9 @@ int lcst::stream_dev_record(StreamDev *s, int64_t key, uint32_t *out) {
 
 int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
                           uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
-                          std::vector<Dead> *dead, const SetWork *set) {
+                          std::vector<Dead> *dead, const SetWork *set, std::vector<Final> *fin) {
     dead->clear();
+    if (fin) fin->clear();
     s->ms[0] = s->ms[1] = s->ms[2] = 0;
     s->set_ms[0] = s->set_ms[1] = 0;
     Push p{n_keys, std::max<int64_t>(n_items, 0), items, ev16, trans, n_ev, n_trans, init_state, set};
@@ -366,5 +501,7 @@ int lcst::stream_dev_push(StreamDev *s, int64_t n_keys, const Item *items, int64
     push_fill(s, p, l);
     const size_t head = p.sets ? l.out_words : std::min<size_t>(l.out_words, 1 + 4 * STREAM_OUT_HEAD);
     LCCHK(push_enqueue(s, x.d, p, l, head));
-    return push_read_lists(s, x.d, p, l, head, dead);
+    LCCHK(push_read_lists(s, x.d, p, l, head, dead));
+    if (s->exact && fin) LCCHK(push_read_finals(s, x.d, n_keys, *dead, fin));
+    return LC_OK;
 }

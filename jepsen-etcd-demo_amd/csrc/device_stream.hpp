@@ -22,7 +22,13 @@ struct Item {
 };
 // A key that died in a launch.
 struct Dead {
-    uint32_t key, status, fail_event, why;  // STREAM_INVALID / STREAM_ERROR; LC_BATCH_E_* bits
+    uint32_t key, status, fail_event, why;  // STREAM_INVALID / STREAM_ERROR / STREAM_BUDGET; LC_BATCH_E_* bits
+};
+// Exact mode (LC_STREAM_EXACT): what a key that is invalid or at the budget
+// leaves beside its verdict, the words lc_check_batch writes for it.
+struct Final {
+    uint32_t peak = 1, n_final = 0;
+    uint64_t cfg[32] = {};  // n_final configs of two words (max_final <= 16)
 };
 
 // The resident set tier's work of a call (LC_STREAM_SET_TIER): keys that
@@ -47,8 +53,12 @@ struct SetWork {
 };
 
 // Refuses (LC_E_UNSUPPORTED) a context with several devices or a
-// communicator, or a budget below the FAST walk's exact range.
-int stream_dev_open(lc_ctx *c, StreamDev **out);
+// communicator, or -- unless `exact` -- a budget below the FAST walk's exact
+// range.  exact: the launches are k_stream_exact's, with the context's budget,
+// and the stream owns final-config arrays beside its records.
+int stream_dev_open(lc_ctx *c, bool exact, StreamDev **out);
+// The context's lc_opts.max_final: configs per key in exact mode's arrays.
+int stream_dev_max_final(const StreamDev *d);
 void stream_dev_close(StreamDev *d);
 // Search the items' words (one k_stream launch on the context's lane 0,
 // joined behind lane 1) and return the keys that died, ascending by key.
@@ -58,7 +68,19 @@ void stream_dev_close(StreamDev *d);
 // (status STREAM_SET_FALLBACK for those that fell back).
 int stream_dev_push(StreamDev *d, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
                     uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
-                    std::vector<Dead> *dead, const SetWork *set = nullptr);
+                    std::vector<Dead> *dead, const SetWork *set = nullptr, std::vector<Final> *fin = nullptr);
+// Exact mode.  fin (may be null: a stream without the flag leaves it empty)
+// gets one entry per entry of `dead`, filled for STREAM_INVALID / STREAM_BUDGET.
+// stream_dev_peaks: every key's running peak from its record's header
+// (out[n_keys]; a fresh record counts 1).  stream_dev_finals: one
+// k_stream_final launch over the live keys `keys` (their end sets' configs
+// into the stream's arrays), then every key's configs and count back:
+// cfg[n_keys * max_final * 2], n_final[n_keys].
+int stream_dev_peaks(StreamDev *d, int64_t n_keys, uint32_t *out);
+int stream_dev_finals(StreamDev *d, int64_t n_keys, const int32_t *keys, int64_t n_live, uint32_t init_state,
+                      uint64_t *cfg, uint32_t *n_final);
+// Device time of the last stream_dev_finals launch, ms.
+double stream_dev_final_ms(const StreamDev *d);
 // The set-record pool: a slot for a migrating key (the pool is allocated on
 // first use and grows geometrically, in chunks that never move), and its return.
 int stream_dev_set_alloc(StreamDev *d, int32_t *slot);

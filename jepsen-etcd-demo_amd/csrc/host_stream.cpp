@@ -23,6 +23,14 @@
 // its pending ops' descriptors by window slot), later to its set record
 // (device_stream_set.hip).  A key the set tier cannot hold falls back to the
 // deferral (stream_plan.hpp stream_set_falls_back) and its slot is reused.
+//
+// With LC_STREAM_EXACT the register tier's launches are k_stream_exact's
+// (device_stream_exact.hip): a key may also die at the budget (:unknown, not on
+// the invalid list), a dead key brings its peak and the final configs of the
+// set before its failing event with it, lc_stream_finish fetches every other
+// key's (k_stream_final; deferred keys from the batch path), and
+// lc_stream_report renders a key's counterexample from the packer's own words
+// and rows (report_core.hpp).
 
 #include <algorithm>
 #include <chrono>
@@ -33,6 +41,7 @@
 
 #include "common.hpp"
 #include "device_stream.hpp"
+#include "report_core.hpp"
 #include "stream_plan.hpp"
 
 namespace {
@@ -91,6 +100,9 @@ struct SKey {
     // ---- the resident set tier (LC_STREAM_SET_TIER)
     int32_t set_slot = -1;           // its set record in the pool, while it is in the set tier
     bool fell_back = false;          // it left the set tier (or could not enter it): checked at finish
+    // ---- exact mode (LC_STREAM_EXACT): the words lc_check_batch writes beside the verdict
+    uint32_t peak = 1;               // a dead key's; every key's after finish
+    std::vector<uint64_t> finals;    // two words per config: a dead key's, every key's after finish
 };
 
 }  // namespace
@@ -116,6 +128,10 @@ struct lc_stream {
     std::vector<uint32_t> trans;
     std::vector<lcst::Dead> dead;
     bool set_tier = false;  // LC_STREAM_SET_TIER, on a stream with a device
+    bool exact = false;     // LC_STREAM_EXACT
+    std::vector<lcst::Final> fin;  // exact mode: beside `dead`, entry for entry
+    double final_ms = 0;    // exact mode: k_stream_final at finish, and the keys it wrote
+    int64_t final_keys = 0;
     std::vector<lcst::SetMig> set_mig;
     std::vector<lcst::SetItem> set_items;
     std::vector<uint32_t> ev32;
@@ -351,7 +367,8 @@ void fall_back(lc_stream *s, SKey &k) {
 // The launch's dead keys into the verdicts; the first key in error (or -1).
 int64_t take_dead(lc_stream *s, uint32_t *why) {
     int64_t bad = -1;
-    for (const lcst::Dead &d : s->dead) {
+    for (size_t di = 0; di < s->dead.size(); ++di) {
+        const lcst::Dead &d = s->dead[di];
         if (d.key >= s->keys.size()) continue;
         SKey &k = s->keys[d.key];
         if (d.status == lc::STREAM_SET_FALLBACK) {  // back to deferral: not dead, checked at finish
@@ -365,11 +382,20 @@ int64_t take_dead(lc_stream *s, uint32_t *why) {
             k.cause = LC_CAUSE_NONLIN;
             k.fail_event = (int32_t)d.fail_event;
             s->invalid_now.push_back((int64_t)d.key);
+        } else if (d.status == lc::STREAM_BUDGET) {  // exact mode: :unknown, not on the invalid list
+            k.valid = LC_UNKNOWN;
+            k.cause = LC_CAUSE_BUDGET;
+            k.fail_event = (int32_t)d.fail_event;
         } else {
             k.valid = LC_UNKNOWN;
             k.cause = LC_CAUSE_ERROR;
             k.fail_event = -1;
             if (bad < 0) { bad = (int64_t)d.key; *why = d.why; }
+        }
+        if (s->exact && di < s->fin.size() && (d.status == lc::STREAM_INVALID || d.status == lc::STREAM_BUDGET)) {
+            const lcst::Final &f = s->fin[di];
+            k.peak = f.peak;
+            k.finals.assign(f.cfg, f.cfg + 2 * (size_t)f.n_final);
         }
     }
     return bad;
@@ -450,7 +476,7 @@ int send_rows(lc_stream *s, int64_t *events) {
                            (int64_t)s->set_items.size(), s->ev32.data(), s->ev32.size()};
     int rc = lcst::stream_dev_push(s->dev, (int64_t)s->keys.size(), s->items.data(), (int64_t)s->items.size(),
                                    s->ev16.data(), s->ev16.size(), s->trans.data(), s->trans.size(), 0, &s->dead,
-                                   s->set_tier ? &sw : nullptr);
+                                   s->set_tier ? &sw : nullptr, &s->fin);
     if (rc) return rc;
     uint32_t why = 0;
     const int64_t bad = take_dead(s, &why);
@@ -465,6 +491,36 @@ int check_mode(lc_stream *s, int mode, const char *fn) {
     if (s->mode && s->mode != mode)
         return lc::fail(LC_E_INVALID, "%s: the stream is in %s mode (fixed by its first call)", fn,
                         s->mode == 1 ? "rows" : "events");
+    return LC_OK;
+}
+
+// Exact mode at finish: the live register-tier keys' end sets (k_stream_final)
+// and every searched key's peak, into the keys.  Keys that died keep what
+// their launch left; deferred keys got theirs from the batch path.
+int finish_exact(lc_stream *s) {
+    const size_t n = s->keys.size();
+    if (!n) return LC_OK;
+    std::vector<int32_t> live;
+    for (size_t ki = 0; ki < n; ++ki) {
+        const SKey &k = s->keys[ki];
+        if (!k.err && !k.dead && k.defer_at < 0) live.push_back((int32_t)ki);
+    }
+    const size_t mf = (size_t)lcst::stream_dev_max_final(s->dev);
+    std::vector<uint64_t> cfg(n * mf * 2 + 1);
+    std::vector<uint32_t> n_final(n), peak(n);
+    int rc = lcst::stream_dev_finals(s->dev, (int64_t)n, live.data(), (int64_t)live.size(), s->init_state, cfg.data(),
+                                     n_final.data());
+    if (rc) return rc;
+    s->final_ms = lcst::stream_dev_final_ms(s->dev);
+    s->final_keys = (int64_t)live.size();
+    rc = lcst::stream_dev_peaks(s->dev, (int64_t)n, peak.data());
+    if (rc) return rc;
+    for (int32_t ki : live) {
+        SKey &k = s->keys[(size_t)ki];
+        k.peak = peak[(size_t)ki];
+        k.finals.assign(cfg.begin() + (std::ptrdiff_t)((size_t)ki * mf * 2),
+                        cfg.begin() + (std::ptrdiff_t)((size_t)ki * mf * 2 + (size_t)n_final[(size_t)ki] * 2));
+    }
     return LC_OK;
 }
 
@@ -487,8 +543,12 @@ extern "C" int lc_stream_open(lc_ctx *ctx, const lc_pack_opts *opts, lc_stream *
 extern "C" int lc_stream_open_opts(lc_ctx *ctx, const lc_pack_opts *opts, const lc_stream_opts *sopts, lc_stream **out) {
     if (!out) return lc::fail(LC_E_INVALID, "lc_stream_open: null out");
     *out = nullptr;
-    if (sopts && (sopts->flags & ~(uint32_t)LC_STREAM_SET_TIER))
+    if (sopts && (sopts->flags & ~(uint32_t)(LC_STREAM_SET_TIER | LC_STREAM_EXACT)))
         return lc::fail(LC_E_INVALID, "lc_stream_open_opts: unknown flags 0x%x", sopts->flags);
+    const bool exact = sopts && (sopts->flags & LC_STREAM_EXACT);
+    if (exact && (sopts->flags & LC_STREAM_SET_TIER))
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open_opts: LC_STREAM_EXACT with LC_STREAM_SET_TIER: the set tier keeps "
+                                          "no sizes and no final configs");
     const int model = opts ? opts->model : LC_MODEL_CAS_REGISTER;
     if (model == LC_MODEL_MULTI_REGISTER)
         return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: multi-register has no register-tier search to resume");
@@ -496,8 +556,9 @@ extern "C" int lc_stream_open_opts(lc_ctx *ctx, const lc_pack_opts *opts, const 
     lc_stream *s = new lc_stream;
     s->ctx = ctx;
     s->model = model;
+    s->exact = exact;
     if (ctx) {
-        int rc = lcst::stream_dev_open(ctx, &s->dev);
+        int rc = lcst::stream_dev_open(ctx, exact, &s->dev);
         if (rc) {
             delete s;
             return rc;
@@ -610,6 +671,18 @@ extern "C" int lc_stream_finish(lc_stream *s, lc_stream_update *u) {
             r.valid = valid.data();
             r.fail_event = fev.data();
             r.cause = cause.data();
+            // exact mode: the keys' full records, as the one-shot check writes them
+            const size_t mf = s->exact ? (size_t)lcst::stream_dev_max_final(s->dev) : 0;
+            std::vector<uint32_t> peak, n_final;
+            std::vector<uint64_t> cfg;
+            if (s->exact) {
+                peak.assign(dk.size(), 0);
+                n_final.assign(dk.size(), 0);
+                cfg.assign(dk.size() * mf * 2 + 1, 0);
+                r.peak_configs = peak.data();
+                r.n_final = n_final.data();
+                r.final_configs = cfg.data();
+            }
             rc = lc_check_batch(s->ctx, &b, &r, nullptr);
             if (rc) return rc;
             for (size_t i = 0; i < dk.size(); ++i) {
@@ -617,10 +690,19 @@ extern "C" int lc_stream_finish(lc_stream *s, lc_stream_update *u) {
                 k.valid = valid[i];
                 k.cause = cause[i];
                 k.fail_event = fev[i];
+                if (s->exact) {
+                    k.peak = peak[i];
+                    const size_t nf = std::min<size_t>(n_final[i], mf);
+                    k.finals.assign(cfg.begin() + (std::ptrdiff_t)(i * mf * 2), cfg.begin() + (std::ptrdiff_t)(i * mf * 2 + nf * 2));
+                }
                 if (valid[i] == LC_INVALID) s->invalid_now.push_back(dk[i]);
             }
             std::sort(s->invalid_now.begin(), s->invalid_now.end());
         }
+    }
+    if (s->exact && s->dev) {
+        int rc = finish_exact(s);
+        if (rc) return rc;
     }
     s->finished = true;
     fill_update(s, u, events);
@@ -699,7 +781,7 @@ extern "C" int lc_stream_push(lc_stream *s, const lc_batch *b, const int64_t *ke
     }
     s->ms[0] = now_ms() - t0;
     rc = lcst::stream_dev_push(s->dev, (int64_t)s->keys.size(), s->items.data(), (int64_t)s->items.size(), s->ev16.data(),
-                               s->ev16.size(), b->trans, (uint64_t)b->n_trans, s->init_state, &s->dead);
+                               s->ev16.size(), b->trans, (uint64_t)b->n_trans, s->init_state, &s->dead, nullptr, &s->fin);
     dev_times(s);
     if (rc) return rc;
     uint32_t why = 0;
@@ -730,7 +812,67 @@ extern "C" int lc_stream_results(lc_stream *s, lc_result *r) {
             r->fail_event[i] = k.fail_event;
         }
     }
+    if (!s->exact) return LC_OK;
+    // exact mode: the rest of the record, where the caller asks for it.  A
+    // key that died or a finished stream: the words kept with the key; a live
+    // key: its running peak from its device record, no configs yet.
+    const size_t n = s->keys.size(), mf = (size_t)lcst::stream_dev_max_final(s->dev);
+    if (r->peak_configs && n) {
+        if (!s->finished) {
+            int rc = lcst::stream_dev_peaks(s->dev, (int64_t)n, r->peak_configs);
+            if (rc) return rc;
+        }
+        for (size_t i = 0; i < n; ++i) {
+            const SKey &k = s->keys[i];
+            if (k.err) r->peak_configs[i] = 0;
+            else if (s->finished || k.dead) r->peak_configs[i] = k.peak;
+        }
+    }
+    for (size_t i = 0; i < n; ++i) {
+        const SKey &k = s->keys[i];
+        const size_t nf = k.err ? 0 : std::min(k.finals.size() / 2, mf);
+        if (r->n_final) r->n_final[i] = (uint32_t)nf;
+        if (r->final_configs) {
+            uint64_t *o = r->final_configs + i * mf * 2;
+            std::fill(o, o + mf * 2, 0ull);
+            std::copy(k.finals.begin(), k.finals.begin() + (std::ptrdiff_t)(nf * 2), o);
+        }
+    }
     return LC_OK;
+}
+
+namespace {
+// A key of a stream as the counterexample's source (report_core.hpp): its own
+// words, transitions, state values and event rows.
+struct StreamSrc {
+    const SKey &k;
+    uint64_t n() const { return k.ev.size(); }
+    uint32_t word(uint64_t j) const { return k.ev[(size_t)j]; }
+    int64_t row(uint64_t j) const { return k.ev_row[(size_t)j]; }
+    uint32_t step(uint32_t w, uint32_t st) const {
+        const uint32_t t = LC_EV_TRANS(w);
+        return t < k.descs.size() ? lcr::desc_step(k.descs[t], st) : LC_STATE_NONE;
+    }
+    int64_t value(uint32_t st) const { return st && st < k.vals.size() ? k.vals[st] : LC_NIL; }
+    // An op in window slot `slot` whose :ok row has arrived but is still held
+    // back behind an open invoke: its event is to come, its row is known.
+    int64_t late_done_row(uint32_t slot) const {
+        for (size_t j = k.held_head; j < k.held.size(); ++j)
+            if (k.held[j].ok && k.ops[(size_t)k.held[j].op].slot == (int16_t)slot) return k.held[j].row;
+        return -1;
+    }
+};
+}  // namespace
+
+extern "C" int64_t lc_stream_report(const lc_stream *s, int64_t i, int32_t valid, int32_t fail_event,
+                                    const uint64_t *final_configs, uint32_t n_final, int32_t max_paths, int64_t *out,
+                                    int64_t cap) {
+    if (!s || i < 0 || i >= (int64_t)s->keys.size()) return lc::fail(LC_E_INVALID, "lc_stream_report: no such key index");
+    if (s->mode == 2)
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_report: a stream in events mode has no history rows to name");
+    const SKey &k = s->keys[(size_t)i];
+    if (k.err) return lc::fail(LC_E_INVALID, "lc_stream_report: key %lld could not be prepared: %s", (long long)i, k.msg.c_str());
+    return lcr::report(StreamSrc{k}, valid, fail_event, final_configs, n_final, max_paths, false, out, cap);
 }
 
 extern "C" int64_t lc_stream_keys(const lc_stream *s, int64_t *out) {
@@ -840,6 +982,13 @@ extern "C" int lc_stream_set_stats(const lc_stream *s, double *out6) {
     if (!s || !out6) return lc::fail(LC_E_INVALID, "lc_stream_set_stats: null argument");
     for (int i = 0; i < 6; ++i) out6[i] = 0;
     if (s->dev) lcst::stream_dev_set_stats(s->dev, out6);
+    return LC_OK;
+}
+
+extern "C" int lc_stream_exact_stats(const lc_stream *s, double *out2) {
+    if (!s || !out2) return lc::fail(LC_E_INVALID, "lc_stream_exact_stats: null argument");
+    out2[0] = s->final_ms;
+    out2[1] = (double)s->final_keys;
     return LC_OK;
 }
 

@@ -1093,11 +1093,14 @@ struct LatWalk {
 
 // A walk's state between two events, for the resume form (k_stream; the
 // record's layout: stream_plan.hpp): in, where the walk starts; out, where
-// it stopped.  The lattice itself is W, or m.W when in_mem.
+// it stopped.  The lattice itself is W, or m.W when in_mem.  `dirty` belongs
+// to the FAST walk's closed sets and `peak` (the largest set so far) to the
+// exact walk: neither reads or writes the other's.
 struct LatResume {
     uint32_t k_v, cap_v, b_v, slot_v, dense_v;  // per-op lanes, as in lattice_walk
     uint32_t n, live;
     bool in_mem, dirty;
+    uint32_t peak;
 };
 
 // The register tier's event walk: events evp[0 .. nev) from the start word
@@ -1111,14 +1114,16 @@ struct LatResume {
 // RESUME: the walk starts from *rs and the lattice the caller loaded (W, or
 // m.W when rs->in_mem) instead of `init`, in the phase its pending count
 // belongs to (7 or more pending: the dense phase), and leaves its state in
-// *rs.  Event ordinals (fev) count from evp[0].
+// *rs.  Event ordinals (fev) count from evp[0].  On the compact build, FAST
+// (k_stream) or exact (k_stream_exact: Knossos's own sets, so sizes, budgets
+// and final configs carry across calls).
 template <int RM, bool FAST, bool TAG, class EvT, bool RESUME = false>
 __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, const EvT evp, const uint32_t nev,
                                              const uint32_t *const trp, const uint32_t ntr, uint32_t init,
                                              const LatMem &m, uint64_t budget, bool want_peak, bool count,
                                              LatResume *rs = nullptr) {
     static_assert(!TAG || (FAST && RM == T0_RSMALL), "tagged words: closed sets on the compact lattice only");
-    static_assert(!RESUME || (FAST && !TAG && RM == T0_RSMALL), "resume: the compact FAST build only");
+    static_assert(!RESUME || (!TAG && RM == T0_RSMALL), "resume: the compact untagged build only");
     const uint32_t lane = lane_id();
     auto ldesc = [&](uint32_t w, bool have) -> uint32_t {
         const uint32_t t = LC_EV_TRANS(w);
@@ -1151,6 +1156,7 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
         in_mem = rs->in_mem;
         k_v = rs->k_v; cap_v = rs->cap_v; b_v = rs->b_v; slot_v = rs->slot_v; dense_v = rs->dense_v;
         n = rs->n; live = rs->live;
+        if constexpr (!FAST) peak = rs->peak;
     }
 
     // Event cursor: events arrive 64 at a time, one per lane; the next
@@ -1195,7 +1201,7 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
     // (stream_plan.hpp stream_resume_phase) and keeps the loaded lattice
     [[maybe_unused]] bool dense_first = false;
     if constexpr (RESUME) {
-        dirty = rs->dirty;
+        if constexpr (FAST) dirty = rs->dirty;
         dense_first = n >= 7;
     }
     for (uint32_t phase = 0; phase <= nev && e < lim; ++phase) {
@@ -1361,7 +1367,9 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
     if constexpr (RESUME) {
         rs->in_mem = in_mem;
         rs->k_v = k_v; rs->cap_v = cap_v; rs->b_v = b_v; rs->slot_v = slot_v; rs->dense_v = dense_v;
-        rs->n = n; rs->live = live; rs->dirty = dirty;
+        rs->n = n; rs->live = live;
+        if constexpr (FAST) rs->dirty = dirty;
+        else rs->peak = peak;
     }
 }
 

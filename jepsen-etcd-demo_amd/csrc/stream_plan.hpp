@@ -28,6 +28,8 @@ constexpr uint32_t STREAM_H_FAIL = 6;     // STREAM_INVALID: ordinal of the fail
 constexpr uint32_t STREAM_H_PEND0 = 7;    // window slots 0..31 pending (the slot protocol)
 constexpr uint32_t STREAM_H_PEND1 = 8;    // window slots 32..63
 constexpr uint32_t STREAM_H_STARTED = 9;  // 0: a fresh (zero-filled) record, the walk starts from the initial state
+constexpr uint32_t STREAM_H_PEAK = 10;    // exact mode: the largest config set so far (a fresh record counts as 1)
+static_assert(STREAM_H_PEAK < STREAM_HDR_WORDS, "the header's spare words hold the peak");
 // per-op lane arrays of the walk, 64 lanes each, in this order
 constexpr uint32_t STREAM_LANE_ARRAYS = 5;  // k_v, cap_v, b_v, slot_v, dense_v
 constexpr uint32_t STREAM_OFF_LANES = STREAM_HDR_WORDS;
@@ -36,6 +38,9 @@ constexpr uint32_t STREAM_LATTICE_MAX = 1024;  // 10 ops pending: 16 registers x
 constexpr uint32_t STREAM_REC_WORDS = STREAM_OFF_LATTICE + STREAM_LATTICE_MAX;
 
 constexpr uint32_t STREAM_LIVE = 0, STREAM_INVALID = 1, STREAM_ERROR = 2;
+// exact mode (LC_STREAM_EXACT): a set or a closure passed the context's budget
+// at event STREAM_H_FAIL.  (3 is the set record's STREAM_SET_FALLBACK.)
+constexpr uint32_t STREAM_BUDGET = 4;
 
 // the register tier's reach (lattice_core.hpp T0_MAX_WIDTH / T0_MAX_STATES)
 constexpr uint32_t STREAM_MAX_WIDTH = 10;
@@ -43,6 +48,21 @@ constexpr uint32_t STREAM_MAX_STATES = 32;
 // the least budget at which the FAST walk's sets are exact: no lattice holds
 // more than 16 registers x 64 lanes x 32 states
 constexpr uint64_t STREAM_MIN_BUDGET = 16ull * 64 * 32;
+// Budgets a stream accepts: the exact walk holds Knossos's own sets and counts
+// them, so any; the FAST walk's closed sets only where no set can pass it.
+constexpr bool stream_budget_ok(uint64_t budget, bool exact) { return exact || budget >= STREAM_MIN_BUDGET; }
+
+// ---- exact mode: the final configs of a stream's keys --------------------------
+// Two arrays in device memory beside the records, grown with them: max_final
+// configs of two 64-bit words per key (write_final_mem's record: the slot
+// mask's low word; state << 48 | its high bits), and a count per key.
+constexpr uint32_t STREAM_MAX_FINAL = 16;  // lc_opts.max_final at most
+constexpr uint64_t stream_final_words64(uint32_t max_final) { return 2ull * max_final; }  // per key
+constexpr uint64_t stream_final_off64(uint64_t key, uint32_t max_final, uint32_t cfg) {
+    return (key * max_final + cfg) * 2;
+}
+constexpr uint64_t stream_final_bytes(uint64_t keys, uint32_t max_final) { return keys * stream_final_words64(max_final) * 8; }
+constexpr uint64_t stream_nfinal_bytes(uint64_t keys) { return keys * 4; }
 
 // Lattice words of a key with n ops pending: one register (64 lanes) up to 6,
 // doubling with every op beyond; word k * 64 + lane = register k of the lane.

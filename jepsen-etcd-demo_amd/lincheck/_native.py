@@ -168,6 +168,7 @@ class LcPerfResult(C.Structure):
 # ---- incremental check (lc_stream_*) -------------------------------------------
 LC_STREAM_REC_WORDS = 1360
 LC_STREAM_SET_TIER = 1
+LC_STREAM_EXACT = 2
 LC_STREAM_TIER_REGISTER, LC_STREAM_TIER_SET, LC_STREAM_TIER_FALLEN_BACK, LC_STREAM_TIER_DEAD = 0, 1, 2, 3
 LC_STREAM_SET_HEAD_WORDS = 80
 
@@ -270,6 +271,9 @@ SIGNATURES = {
     "lc_stream_push": (C.c_int, [C.c_void_p, P(LcBatch), P(C.c_int64), P(LcStreamUpdate)]),
     "lc_stream_finish": (C.c_int, [C.c_void_p, P(LcStreamUpdate)]),
     "lc_stream_results": (C.c_int, [C.c_void_p, P(LcResult)]),
+    "lc_stream_exact_stats": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_stream_report": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, P(C.c_uint64), C.c_uint32, C.c_int32,
+                                     P(C.c_int64), C.c_int64]),
     "lc_stream_keys": (C.c_int64, [C.c_void_p, P(C.c_int64)]),
     "lc_stream_key_events": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_int64)]),
     "lc_stream_event_row": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int64]),

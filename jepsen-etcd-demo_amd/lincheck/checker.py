@@ -417,16 +417,23 @@ def _render_key(packed: Packed, i: int, res: KeyResults, sub_rows: Optional[np.n
         # only (as gpu_checker.clj, which skips lc_report here too)
         return {"analyzer": analyzer, "configs": [], "final-paths": [], "valid?": True}
     w = _report(packed, i, res, analyzer).tolist()  # Python ints: no numpy scalar per word
+    state_map = (lambda x: packed.state_map(i, x)) if isinstance(packed.model, MultiRegister) else None
+    return _render_words(w, v, cause, analyzer, packed.hist, packed.model, state_map)
+
+
+def _render_words(w: List[int], v: int, cause: str, analyzer: str, hist: History, model, state_map=None) -> Dict:
+    """The result map of a key that is not valid from its report words
+    (lc_report, lc_report_wgl, lc_stream_report): rows name ops of `hist`."""
     ops: Dict[tuple, Dict] = {}
 
     def op(inv: int, done: int) -> Dict:
         """The invocation as knossos.history/complete leaves it: it takes its
         completion's :value when it has none."""
         if (inv, done) not in ops:
-            o = _sub_op(packed, inv)
+            o = hist.sub_op(inv)
             if done >= 0 and (o.get("value") is None or o.get("f") == "txn"):
                 # a :txn takes its completion's micro-ops when it has some
-                dv = _sub_op(packed, done).get("value")
+                dv = hist.sub_op(done).get("value")
                 if dv is not None or o.get("f") != "txn":
                     o["value"] = dv
             ops[(inv, done)] = o
@@ -437,10 +444,10 @@ def _render_key(packed: Packed, i: int, res: KeyResults, sub_rows: Optional[np.n
     def state_of(x: int):
         got = states.get(x)
         if got is None:
-            if isinstance(packed.model, MultiRegister):
-                st = packed.model.of_map(packed.state_map(i, x))
+            if state_map is not None:
+                st = model.of_map(state_map(x))
             else:
-                st = packed.model.of_state(None if x == N.LC_NIL else x)
+                st = model.of_state(None if x == N.LC_NIL else x)
             got = states[x] = (st, st.render())
         return got
 
@@ -451,7 +458,7 @@ def _render_key(packed: Packed, i: int, res: KeyResults, sub_rows: Optional[np.n
         return state_of(x)[1]
 
     op_row, prev_row, n_cfg, n_paths = w[:4]
-    prev = _sub_op(packed, prev_row) if prev_row >= 0 else None
+    prev = hist.sub_op(prev_row) if prev_row >= 0 else None
     at = 4
     configs = []
     for _ in range(n_cfg):
@@ -463,7 +470,7 @@ def _render_key(packed: Packed, i: int, res: KeyResults, sub_rows: Optional[np.n
             at += 2 * n
         configs.append({"model": st, "last-op": prev, "pending": lists[0], "linearized": lists[1]})
     paths = []
-    fail_op = _sub_op(packed, op_row) if op_row >= 0 else None
+    fail_op = hist.sub_op(op_row) if op_row >= 0 else None
     for _ in range(n_paths):
         path = [{"op": prev, "model": rendered(w[at])}]
         n = w[at + 1]; at += 2
@@ -536,16 +543,18 @@ class Linearizable:
     def _dev(self) -> Device:
         return device_for(self.device, self.budget, self.algorithm)
 
-    def stream(self, dev: Optional[Device] = None, set_tier: bool = False):
+    def stream(self, dev: Optional[Device] = None, set_tier: bool = False, exact: bool = False):
         """An incremental check of this checker's model (lincheck.stream.Stream):
         rows are appended while the test runs and verdicts come back online.
         set_tier: keys past the register tier keep being searched online too.
+        exact: the stream keeps Knossos's exact sets -- any :max-configs, peaks,
+        final configs and `Stream.analysis` online (not with set_tier).
         :algorithm :wgl has no resident search and raises."""
         from .stream import Stream
         if self.algorithm == N.LC_ALGO_WGL:
             raise NotImplementedError("a stream runs the :linear search; :wgl has no state to resume")
         return Stream(dev if dev is not None else device_for(self.device, self.budget, N.LC_ALGO_LINEAR), self.model,
-                      set_tier=set_tier)
+                      set_tier=set_tier, exact=exact)
 
     def check(self, test: Dict, history, opts: Dict | None = None) -> Dict:
         """One key's (unwrapped) sub-history, as at etcdemo.clj:117."""

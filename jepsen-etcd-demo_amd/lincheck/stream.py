@@ -10,11 +10,19 @@
     res = s.results()                # valid / cause / fail_event per key
 
 Each call searches only the events that are new; a key's verdict after
-`finish` equals `Packed` + `Device.check` on the whole history.  A stream
-returns verdicts and failing events only, no final configs: to render the
-counterexample of a key found invalid, run the ordinary checker
+`finish` equals `Packed` + `Device.check` on the whole history.  By default a
+stream returns verdicts and failing events only, no final configs: to render
+the counterexample of a key found invalid, run the ordinary checker
 (`checker.linearizable(...).check`) on that key's sub-history.
 `failing_row(i)` names the history row of the :ok that could not be linearized.
+
+`Stream(dev, exact=True)` keeps Knossos's exact config set of every
+register-tier key on the device (LC_STREAM_EXACT): any budget is accepted and
+a key that passes it turns :unknown in the append that reaches the event;
+`results()` also carries `peak`, `final` and `n_final` -- a dead key's at
+once, every key's after `finish`, equal to the one-shot check's -- and
+`analysis(i, history)` renders a key's counterexample (:op, :previous-ok,
+:configs, :final-paths) right after the append that reported it.
 
 `Stream(dev, set_tier=True)` keeps a key that passes 10 pending ops or 32
 register values on the device too (the resident set tier): it is reported
@@ -53,8 +61,12 @@ class Update:
 
 
 class StreamResults:
-    def __init__(self, keys, valid, fail_event, cause):
+    """valid / fail_event / cause per key; of an exact stream also peak,
+    final ([key][max_final][2] words as Device.check's) and n_final (else None)."""
+
+    def __init__(self, keys, valid, fail_event, cause, peak=None, final=None, n_final=None):
         self.keys, self.valid, self.fail_event, self.cause = keys, valid, fail_event, cause
+        self.peak, self.final, self.n_final = peak, final, n_final
 
 
 class Stream:
@@ -63,17 +75,20 @@ class Stream:
 
     TIERS = ("register", "set", "fallen_back", "dead")
 
-    def __init__(self, dev=None, model=None, set_tier=False):
+    def __init__(self, dev=None, model=None, set_tier=False, exact=False):
         """set_tier: a key that leaves the register tier (10 ops pending, 32
         states) migrates to the resident set tier and keeps being searched
-        online, instead of waiting for `finish` (LC_STREAM_SET_TIER)."""
+        online, instead of waiting for `finish` (LC_STREAM_SET_TIER).
+        exact: the register tier keeps Knossos's exact sets (LC_STREAM_EXACT;
+        not together with set_tier)."""
         self.model = model if model is not None else CASRegister()
         if isinstance(self.model, MultiRegister):
             raise NotImplementedError("a stream checks (model/cas-register), (model/register) and (model/mutex)")
         self.dev = dev  # keeps the context alive
         opts = N.LcPackOpts(self.model.code)
         h = C.c_void_p()
-        sopts = N.LcStreamOpts(N.LC_STREAM_SET_TIER if set_tier else 0)
+        self.exact = bool(exact)
+        sopts = N.LcStreamOpts((N.LC_STREAM_SET_TIER if set_tier else 0) | (N.LC_STREAM_EXACT if exact else 0))
         N.check(N.lib().lc_stream_open_opts(dev.handle if dev is not None else None, C.byref(opts), C.byref(sopts),
                                             C.byref(h)))
         self.handle = h
@@ -132,9 +147,45 @@ class Stream:
         valid, fev, cause = np.zeros(n, np.int8), np.zeros(n, np.int32), np.zeros(n, np.uint8)
         r = N.LcResult()
         r.valid, r.fail_event, r.cause = N.ptr(valid, C.c_int8), N.ptr(fev, C.c_int32), N.ptr(cause, C.c_uint8)
-        N.check(N.lib().lc_stream_results(self.handle, C.byref(r)))
         k = len(keys)
-        return StreamResults(keys, valid[:k], fev[:k], cause[:k])
+        if not self.exact or self.dev is None:  # (a packer-only stream: the call says so)
+            N.check(N.lib().lc_stream_results(self.handle, C.byref(r)))
+            return StreamResults(keys, valid[:k], fev[:k], cause[:k])
+        mf = self.dev.max_final
+        peak, n_final = np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        final = np.zeros((n, mf, 2), np.uint64)
+        r.peak_configs, r.n_final = N.ptr(peak, C.c_uint32), N.ptr(n_final, C.c_uint32)
+        r.final_configs = N.ptr(final, C.c_uint64)
+        N.check(N.lib().lc_stream_results(self.handle, C.byref(r)))
+        return StreamResults(keys, valid[:k], fev[:k], cause[:k], peak[:k], final[:k], n_final[:k])
+
+    def analysis(self, i: int, history, res: Optional[StreamResults] = None) -> dict:
+        """Knossos's analysis of key i as the ordinary checker renders it
+        (:valid?, :op, :previous-ok, :last-op, :configs, :final-paths), from an
+        exact stream in rows mode.  `history` is the caller's concatenation of
+        everything appended so far (a History, or a list of op maps): the
+        stream keeps no copy of the rows.  res: a `results()` taken since the
+        key's verdict, to spare the call."""
+        from .checker import TRUNCATE, _render_words
+        if not self.exact:
+            raise ValueError("analysis needs Stream(dev, exact=True): a plain stream keeps no final configs")
+        res = res if res is not None else self.results()
+        v, c = int(res.valid[i]), int(res.cause[i])
+        if v == N.LC_UNKNOWN and c == N.LC_CAUSE_ERROR:
+            return {"valid?": "unknown", "error": self.key_error(i) or "error"}
+        if v == N.LC_VALID:
+            return {"analyzer": "linear", "configs": [], "final-paths": [], "valid?": True}
+        hist = history if isinstance(history, History) else History.from_ops(history)
+        fin = np.ascontiguousarray(res.final[i], dtype=np.uint64)
+        cap = 4096
+        while True:
+            buf = np.empty(cap, np.int64)
+            n = N.check(N.lib().lc_stream_report(self.handle, i, v, int(res.fail_event[i]), N.ptr(fin, C.c_uint64),
+                                                 int(res.n_final[i]), TRUNCATE, N.ptr(buf, C.c_int64), cap))
+            if n <= cap:
+                break
+            cap = n
+        return _render_words(buf[:n].tolist(), v, N.CAUSES.get(c, "error"), "linear", hist, self.model)
 
     def key_events(self, i: int) -> dict:
         out = np.zeros(4, np.int64)
@@ -206,6 +257,12 @@ class Stream:
         N.check(N.lib().lc_stream_set_stats(self.handle, N.ptr(out, C.c_double)))
         return {"migrate_ms": float(out[0]), "set_kernel_ms": float(out[1]), "pool_slots": int(out[2]),
                 "pool_in_use": int(out[3]), "pool_peak": int(out[4]), "slot_bytes": int(out[5])}
+
+    def exact_stats(self) -> dict:
+        """Exact mode: k_stream_final's device time at `finish`, ms."""
+        out = np.zeros(2, np.float64)
+        N.check(N.lib().lc_stream_exact_stats(self.handle, N.ptr(out, C.c_double)))
+        return {"final_kernel_ms": float(out[0]), "final_keys": int(out[1])}
 
     def last_timing(self) -> dict:
         out = np.zeros(4, np.float64)

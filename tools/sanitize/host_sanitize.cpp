@@ -5,7 +5,9 @@
 // -fsanitize=thread (make tsan) and driven over generated histories, round
 // trips through history.edn and test.fressian, the parallel EDN split (files
 // above 1 MB), mangled EDN text and Fressian bytes, and malformed op
-// sequences.  Exit status 0 = every check passed and no sanitizer fired.
+// sequences; and the streaming packer with lc_stream_report (a packer-only
+// LC_STREAM_EXACT stream fed in pieces, reports asked for while rows are still
+// held back).  Exit status 0 = every check passed and no sanitizer fired.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,6 +38,8 @@ static int failures = 0;
             ++failures;                                                            \
         }                                                                          \
     } while (0)
+
+static void exercise_stream(const lc_history &h, int model);
 
 // pack, render every key's report, run the oracle; returns keys
 static int64_t exercise(const lc_history &h, int model, const int64_t *init = nullptr, int32_t n_init = 0) {
@@ -82,6 +86,7 @@ static int64_t exercise(const lc_history &h, int model, const int64_t *init = nu
     }
     const int64_t nk = b.n_keys;
     lc_packed_free(p);
+    if (!init && h.n <= 40000) exercise_stream(h, model);  // (the 3,000-key shape is for the EDN split)
     if (model == LC_MODEL_MULTI_REGISTER) return nk;  // the C oracle has no table models
     int64_t ok = oracle_check_history_model(&h, model, 1 << 14, 4, nullptr, nullptr, 0);
     if (ok > 0) {
@@ -90,6 +95,61 @@ static int64_t exercise(const lc_history &h, int model, const int64_t *init = nu
         CHECK(oracle_check_history_model(&h, model, 1 << 14, 4, ok_keys.data(), res.data(), ok) == ok);
     }
     return nk;
+}
+
+// The same history through a packer-only exact stream, 97 rows per append:
+// after every append and after finish, each key's report with made-up final
+// configs (any state id of the key, any slots), at a failing event anywhere in
+// its decided prefix -- ops whose :ok row is still held back included.
+static void exercise_stream(const lc_history &h, int model) {
+    lc_pack_opts po{model, 0, nullptr};
+    lc_stream_opts so{LC_STREAM_EXACT};
+    lc_stream *s = nullptr;
+    if (lc_stream_open_opts(nullptr, &po, &so, &s) != LC_OK) return;  // (multi-register: no stream)
+    std::mt19937_64 rng(11);
+    std::vector<int64_t> w(4096);
+    auto reports = [&]() {
+        const int64_t nk = lc_stream_keys(s, nullptr);
+        for (int64_t i = 0; i < nk; i += 1 + (int64_t)(rng() % 3)) {
+            int64_t ev[4];
+            CHECK(lc_stream_key_events(s, i, ev) == LC_OK);
+            uint32_t ns = 1;
+            int64_t val;
+            int nil;
+            while (ns < 64 && lc_stream_state_value(s, i, ns, &val, &nil) == LC_OK) ++ns;
+            uint64_t fin[2 * 10];
+            const uint32_t nf = (uint32_t)(rng() % 11);
+            for (uint32_t c = 0; c < nf; ++c) {
+                fin[2 * c] = rng();
+                fin[2 * c + 1] = ((uint64_t)(rng() % ns) << 48) | (rng() & 0xFFFFFFull);
+            }
+            const int32_t fe = ev[0] ? (int32_t)(rng() % (uint64_t)ev[0]) : -1;
+            for (int valid : {LC_VALID, LC_INVALID, LC_UNKNOWN}) {
+                const int64_t need = lc_stream_report(s, i, valid, valid == LC_VALID ? -1 : fe, fin, nf, 10, w.data(),
+                                                      (int64_t)w.size());
+                if (lc_stream_key_error(s, i)) { CHECK(need < 0); continue; }
+                CHECK(need >= 4);
+                if (need > (int64_t)w.size()) {
+                    w.resize((size_t)need);
+                    CHECK(lc_stream_report(s, i, valid, valid == LC_VALID ? -1 : fe, fin, nf, 10, w.data(), need) == need);
+                }
+            }
+        }
+    };
+    for (int64_t lo = 0; lo < h.n; lo += 97) {
+        lc_history part = h;
+        part.n = std::min<int64_t>(97, h.n - lo);
+        part.type += lo; part.f += lo; part.process += lo; part.key += lo; part.v0 += lo; part.v1 += lo;
+        if (part.index) part.index += lo;
+        part.mop_off = part.mop = nullptr;  // (a :txn row is refused before either is read)
+        lc_stream_update u;
+        if (lc_stream_append(s, &part, &u) != LC_OK) break;  // a row no stream holds: refused whole
+        if (lo / 97 % 8 == 0) reports();
+    }
+    lc_stream_update u;
+    CHECK(lc_stream_finish(s, &u) == LC_OK);
+    reports();
+    lc_stream_close(s);
 }
 
 static std::string slurp(const char *path) {

@@ -28,6 +28,16 @@ process, after a warm-up round, records checked equal:
   from-scratch  what a caller had to do before: pack and check rows[0:r_i]
                 again at each of the 20 points
 
+--exact on|off times the exact mode (Stream(dev, exact=True)) against the plain
+stream on shapes (a) and (b, 20 appends) and on (e), C5's history merged
+round-robin (5 % anomalies: keys die online), without the one-shot and
+from-scratch comparisons: per-append time, the register tier's kernel
+(k_stream_exact or k_stream) device time, and with `on` k_stream_final at
+finish and -- (e) -- what the exact mode replaces: one lc_pack +
+lc_check_batch with final configs of the invalid keys' sub-histories.  One
+form per process, so that forms and trees alternate in one session; --tree
+runs another checkout's package (the parent commit's, option off).
+
 --profile runs rocprofv3 --kernel-trace --stats in a run of its own (this
 script as the child, shape b, 20 appends, once) and reports k_stream's row.
 
@@ -46,7 +56,8 @@ import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, "jepsen-etcd-demo_amd"))
+TREE = next((sys.argv[i + 1] for i, x in enumerate(sys.argv[:-1]) if x == "--tree"), ROOT)
+sys.path.insert(0, os.path.join(TREE, "jepsen-etcd-demo_amd"))
 
 HDR, LANES = 16, 5 * 64  # stream_plan.hpp
 
@@ -97,12 +108,12 @@ def state_bytes(s, searched_after):
     return rd, wr
 
 
-def run_stream(dev, h, n_appends, want=None, bytes_too=False, set_tier=False):
+def run_stream(dev, h, n_appends, want=None, bytes_too=False, set_tier=False, exact=False):
     import numpy as np
     from lincheck.stream import Stream
     n = len(h)
     step = -(-n // n_appends)
-    s = Stream(dev, set_tier=set_tier)
+    s = Stream(dev, set_tier=set_tier, exact=True) if exact else Stream(dev, set_tier=set_tier)
     per, searched = [], []
     pool_peak = 0
     for lo in range(0, n, step):
@@ -134,6 +145,12 @@ def run_stream(dev, h, n_appends, want=None, bytes_too=False, set_tier=False):
                    pool=dict(slot_bytes=st["slot_bytes"], slots_allocated=st["pool_slots"], peak_in_use=st["pool_peak"],
                              peak_bytes=st["pool_peak"] * st["slot_bytes"],
                              allocated_bytes=st["pool_slots"] * st["slot_bytes"]))
+    if exact:
+        out["final_kernel_ms"] = s.exact_stats()["final_kernel_ms"]
+        out["n_invalid"] = int((res.valid == 0).sum())
+        if want is not None and want.n_final is not None:
+            assert np.array_equal(res.peak, want.peak) and np.array_equal(res.n_final, want.n_final), \
+                "exact stream records differ from the one-shot check"
     if bytes_too:
         searched.append([s.key_events(i)["searched"] for i in range(len(res.keys))])
         rd, wr = state_bytes(s, searched[:-1] if len(searched) > len(per) else searched)
@@ -234,6 +251,41 @@ def shape_d(dev, reps, info_rate):
     return out
 
 
+def shape_exact(dev, name, reps, on):
+    """One form (exact on / off) of shape a, b (20 appends) or e."""
+    import numpy as np
+    from lincheck import history as H
+    from lincheck.checker import Packed
+    if name == "a":
+        h = H.synth(**H.CONFIGS["C1"])
+        n_app = -(-len(h) // 100)
+    else:
+        h = merged_round_robin(H.synth(**H.CONFIGS["C2" if name == "b" else "C5"]))
+        n_app = 20
+    want = dev.check(Packed(h)) if on else one_shot(dev, h)[1]
+    run_stream(dev, h, n_app, want, exact=on)  # warm-up
+    out = dict(shape=name, rows=len(h), appends=n_app, exact=on, runs=[])
+    for _ in range(reps):
+        run = run_stream(dev, h, n_app, want, exact=on)
+        d = digest(run)
+        d["kernel_ms"]["sum"] = sum(p["kernel_ms"] for p in run["per_append"])
+        if on:
+            d["final_kernel_ms"], d["n_invalid"] = run["final_kernel_ms"], run["n_invalid"]
+        out["runs"].append(d)
+    bad = np.flatnonzero(want.valid == 0)
+    if on and len(bad):  # what the exact mode replaces: pack and search the invalid keys again, final configs asked for
+        keys = [Packed(h).keys[i] for i in bad]
+        alt = []
+        for _ in range(reps + 1):
+            t0 = time.perf_counter()
+            pk = Packed(h.select_keys(keys))
+            t1 = time.perf_counter()
+            r = dev.check(pk, peaks=False)
+            alt.append(dict(pack_ms=(t1 - t0) * 1e3, check_ms=(time.perf_counter() - t1) * 1e3, kernel_ms=r.stats["kernel_ms"]))
+        out["research_invalid_keys"] = dict(keys=len(keys), runs=alt[1:])
+    return out
+
+
 def profile():
     """k_stream's row of rocprofv3 --kernel-trace --stats, in a run of its own."""
     d = tempfile.mkdtemp(prefix="stream_prof_")
@@ -254,6 +306,8 @@ def main():
     ap.add_argument("--appends", default="20,200", help="shape b: the append counts")
     ap.add_argument("--d-info-rate", type=float, default=0.02, help="shape d: 0.02 (seed 11) or 0.05 (seed 12)")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--exact", choices=("on", "off"), help="time the exact mode's form on shapes a, b, e (see above)")
+    ap.add_argument("--tree", default=ROOT, help="the checkout whose package runs (default: this one)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "stream_timing.json"))
     a = ap.parse_args()
     from lincheck import _native as N
@@ -263,7 +317,9 @@ def main():
     dev = Device(0)
     doc = {"shapes": []}
     for sh in a.shapes.split(","):
-        if sh == "a":
+        if a.exact:
+            doc["shapes"].append(shape_exact(dev, sh, a.reps, a.exact == "on"))
+        elif sh == "a":
             doc["shapes"].append(shape_a(dev, a.reps))
         elif sh == "b":
             doc["shapes"].append(shape_b(dev, a.reps, tuple(int(x) for x in a.appends.split(","))))
