@@ -1154,10 +1154,10 @@ static lcd::SpecLaunch spec_launch(const Step &s) {
     // (spec_ck == 0: the defaults; else (ck1 + 1) | (ck2 + 1) << 16)
     l.ck1 = o.spec_ck ? ((uint32_t)o.spec_ck & 0xFFFFu) - 1u : 32u;
     l.ck2 = o.spec_ck ? ((uint32_t)o.spec_ck >> 16) - 1u : 120u;
-    // the rerun launch usually finds no key, so one block per CU keeps its
-    // dispatch short; a longer rerun list walks the grid (16 and 64 blocks
-    // measured the same as 256 on C2 in round 5, 0.2552-0.2556 ms per step)
-    l.rerun_grid = c->cu_count;
+    // the rerun launch usually finds no key: a few one-wave blocks, so that
+    // its dispatch never queues behind the other lane's k_spec blocks; a
+    // longer rerun list walks the grid (step_plan.hpp)
+    l.rerun_grid = s.p.rerun_grid;
     l.validate_blocks = s.p.spec_vblocks;
     l.events16 = s.p.ev16 ? s.d->events16 : nullptr;
     l.cost_cuts = (o.path_flags & LC_PATH_SPEC_COST) != 0;
@@ -1166,7 +1166,11 @@ static lcd::SpecLaunch spec_launch(const Step &s) {
     // fresh blocks would all outrank this one's tail, wave age alone measured
     // better (C2, 200 overlapping steps: 0.1735 against 0.1796 ms per step;
     // one search at a time 0.2130 with it, 0.2568 without)
-    l.prio = !(o.path_flags & LC_PATH_SPEC_NOPRIO) && !(s.lu && s.lu->overlap);
+    // (A/B: make variant VFLAGS=-DLC_SPEC_PRIO_OVERLAP=1 keeps it on there)
+#ifndef LC_SPEC_PRIO_OVERLAP
+#define LC_SPEC_PRIO_OVERLAP 0
+#endif
+    l.prio = !(o.path_flags & LC_PATH_SPEC_NOPRIO) && (LC_SPEC_PRIO_OVERLAP || !(s.lu && s.lu->overlap));
     l.vfirst = s.p.spec_vfirst;
     l.fin = s.p.exact ? s.L->spec_fin : nullptr;
     l.stage = !(o.path_flags & LC_PATH_SPEC_NOSTAGE);

@@ -235,7 +235,8 @@ struct SpecLaunch {
     int parity;                // picks this launch's count, which must be zero (both are before the
                                // first launch; k_spec_rerun zeroes the other); alternates
     uint32_t ck1, ck2;         // checkpoint distances of the verifying runs
-    int rerun_grid;            // workgroups of the rerun launch at most
+    int rerun_grid;            // one-wave workgroups of the rerun launch (StepPlan::rerun_grid); wave b works
+                               // in slot b of ws, so at most n_order * segs of them are launched
     int validate_blocks;       // > 0: the T0_STRICT validation runs in that many extra blocks
     const uint16_t *events16;  // the batch's 16-bit event words (read in place), or null (the 32-bit words)
     bool cost_cuts;            // cuts at equal estimated cost instead of equal event counts

@@ -816,11 +816,16 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
     const uint32_t *const trp = KA.trans + (ntr ? tb : 0u);
     const uint32_t nstates = KA.trans_off ? (KA.key_states ? KA.key_states[key] : 0xFFFFu) : KA.shared_states;
     const uint32_t width = KA.key_width ? KA.key_width[key] : 0xFFu;
-    // keys for the unsegmented search: errors, keys outside the tier (it
-    // reports them), and keys too short to cut
-    const bool plain = (KA.key_error && KA.key_error[key]) || nstates > T0_MAX_STATES || nstates == 0 ||
-                       width > T0_MAX_WIDTH || KA.init_state >= T0_MAX_STATES || nev < 2 * SPEC_MIN_LEN;
-    const uint32_t eff = plain ? 1u : min((uint32_t)S, nev / SPEC_MIN_LEN);
+    // keys no wave walks: errors and keys outside the tier, which the verdict
+    // step finishes as lattice_key's prologue does
+    const bool plain = (KA.key_error && KA.key_error[key]) ||
+                       (KA.key_states && KA.key_states[key] > LC_WIDE_MAX_STATES) || nstates > T0_MAX_STATES ||
+                       width > T0_MAX_WIDTH || KA.init_state >= T0_MAX_STATES;
+    // a key too short to cut is one segment: wave 0's exact walk of segment 0
+    // from the initial state is the key's verdict (eff = max(1, min(S, nev /
+    // SPEC_MIN_LEN)) for every key that is walked)
+    const bool whole = plain || nstates == 0 || nev < 2 * SPEC_MIN_LEN;
+    const uint32_t eff = whole ? 1u : min((uint32_t)S, nev / SPEC_MIN_LEN);
     const uint32_t topmask = nstates >= 32 ? ~0u : (1u << nstates) - 1u;
 
     if (threadIdx.x < NWS) s_ws_busy[threadIdx.x] = 0;
@@ -1066,7 +1071,7 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
     // 3. the key's verdict: the first segment whose real run dies
     if (wv == 0) {
         const Args &f = *KA.full;
-        bool rerun = plain, bad = false;
+        bool rerun = false, bad = false;
         int32_t fv = -1;
         // EX: the run whose set is the key's final one -- 2 x segment, + 1 for
         // the verifying run: the run that truly died, or the last segment's
@@ -1091,13 +1096,18 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
         int kr = K_DONE;
         // the unsegmented search runs in a launch of its own (k_spec_rerun):
         // inlined here it cost this kernel 27 VGPRs, 6 -> 4 waves per SIMD
-        if (rerun) {
+        if (plain) {  // in lattice_key's order: the packer's mark, the states, the tier
+            if (KA.key_error && KA.key_error[key]) finish_key(f, key, LC_UNKNOWN, LC_CAUSE_ERROR, -1, 0, 0, 0);
+            else if (KA.key_states && KA.key_states[key] > LC_WIDE_MAX_STATES)
+                finish_key(f, key, LC_UNKNOWN, LC_CAUSE_STATES, -1, 1, 0, 0);
+            else kr = K_SPILL;
+        } else if (rerun) {
             if (lane == 0) KA.spec_rr[atomicAdd(KA.spec_nrr, 1)] = key;
         } else if (bad) kr = K_SPILL;
         else if (fv >= 0) finish_key(f, key, LC_INVALID, LC_CAUSE_NONLIN, fv, 0, 0, (uint64_t)fv + 1u);
         else finish_key(f, key, LC_VALID, LC_CAUSE_NONE, -1, 0, 0, nev);
         if constexpr (EX) {
-            if (!rerun && !bad) {
+            if (!plain && !rerun && !bad) {
                 uint32_t *const sv = KA.spec_fin + ((size_t)blk * S * 2 + fin_run) * SPEC_SAVE_WORDS;
                 const LatMem fm{sv, sv, sv};
                 write_final_mem(f, key, fm, lane, sv[T0_RMEM * 64 + lane], uni(sv[(T0_RMEM + 1) * 64]));
@@ -1116,18 +1126,23 @@ __global__ __launch_bounds__(64 * S, (S == 2 ? LC_SPEC2_WAVES : S == 8 ? LC_SPEC
 }
 #undef KA
 
-// The keys k_spec left to the unsegmented search (compact T0, FAST).
-constexpr int SPEC_RERUN_WAVES = 4;
+// The keys k_spec left to the unsegmented search (compact T0, FAST): runs
+// that never met, lost their pending set or gave up a wait.  One wave per
+// workgroup, no LDS and at most 128 VGPRs (tests/test_rerun_metadata.py), so
+// a block fits wherever one k_spec<8> workgroup of the other lane's launch
+// has ended (4 of them fill a CU's LDS, 8 of their 64-VGPR waves a SIMD): the
+// launch is in every step and usually finds no key, so its dispatch is what
+// it costs.  Wave b's 9-10-pending workspace is slot b of the lane's own
+// k_spec workspaces (a.lat_ws), free once that k_spec has ended -- this
+// launch follows it in stream order -- so an :ok there takes ~40k cycles
+// against ~2k in LDS (spec_walk's note): accepted on a path no measured
+// history takes.  The grid is StepPlan::rerun_grid, at most the slots.
 template <bool E16, bool EX = false>
-__global__ __launch_bounds__(64 * SPEC_RERUN_WAVES) void k_spec_rerun(T0Args a) {
-    // a few workgroups of several waves: the launch is in every step and
-    // usually finds no key, so its dispatch is what it costs
-    __shared__ uint32_t ws_all[SPEC_RERUN_WAVES][3 * T0_RMEM * 64];
-    uint32_t *const ws = ws_all[threadIdx.x >> 6];
+__global__ __launch_bounds__(64) void k_spec_rerun(T0Args a) {
+    uint32_t *const ws = a.lat_ws + (size_t)blockIdx.x * (3 * T0_RMEM * 64);
     const int32_t n = *a.spec_nrr;
     if (blockIdx.x == 0 && threadIdx.x == 0) *a.spec_nrr_next = 0;  // two counters in turn: no memset per step
-    for (int32_t w = blockIdx.x * SPEC_RERUN_WAVES + (int32_t)(threadIdx.x >> 6); w < n;
-         w += gridDim.x * SPEC_RERUN_WAVES) {
+    for (int32_t w = (int32_t)blockIdx.x; w < n; w += (int32_t)gridDim.x) {
         const int32_t key = a.spec_rr[w];
         const int kr = lattice_key<T0_RSMALL, !EX, E16>(a, key, ws);
         if (kr == K_SPILL) t0_spill(a, key);
@@ -1166,7 +1181,8 @@ hipError_t launch_spec(const Args &a, const Args *a_dev, const SpecLaunch &l, hi
     t.spec_rr = l.rr + 2;
     t.spec_fin = fin;
     const dim3 grid((unsigned)std::max(1, a.n_order + std::max(0, l.validate_blocks)));
-    const dim3 rgrid((unsigned)std::max(1, std::min((a.n_order + SPEC_RERUN_WAVES - 1) / SPEC_RERUN_WAVES, l.rerun_grid)));
+    // (one wave each, wave b on workspace slot b: never more than the slots)
+    const dim3 rgrid((unsigned)std::max(1, std::min(a.n_order * segs, l.rerun_grid)));
     // one wave per segment: more segments than waves (8, 12 or 16 on 4
     // waves, 4 or 8 on 2) measured slower (step_plan.hpp)
 #define LC_SPEC_L(SS, E, X) hipLaunchKernelGGL((k_spec<SS, E, X>), grid, dim3(64 * SS), 0, s, t)
@@ -1186,11 +1202,11 @@ hipError_t launch_spec(const Args &a, const Args *a_dev, const SpecLaunch &l, hi
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (events16) {
-        if (fin) hipLaunchKernelGGL((k_spec_rerun<true, true>), rgrid, dim3(64 * SPEC_RERUN_WAVES), 0, s, t);
-        else hipLaunchKernelGGL((k_spec_rerun<true, false>), rgrid, dim3(64 * SPEC_RERUN_WAVES), 0, s, t);
+        if (fin) hipLaunchKernelGGL((k_spec_rerun<true, true>), rgrid, dim3(64), 0, s, t);
+        else hipLaunchKernelGGL((k_spec_rerun<true, false>), rgrid, dim3(64), 0, s, t);
     } else {
-        if (fin) hipLaunchKernelGGL((k_spec_rerun<false, true>), rgrid, dim3(64 * SPEC_RERUN_WAVES), 0, s, t);
-        else hipLaunchKernelGGL((k_spec_rerun<false, false>), rgrid, dim3(64 * SPEC_RERUN_WAVES), 0, s, t);
+        if (fin) hipLaunchKernelGGL((k_spec_rerun<false, true>), rgrid, dim3(64), 0, s, t);
+        else hipLaunchKernelGGL((k_spec_rerun<false, false>), rgrid, dim3(64), 0, s, t);
     }
     return hipGetLastError();
 }

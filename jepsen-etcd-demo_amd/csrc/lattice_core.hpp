@@ -301,7 +301,8 @@ struct T0Args {
     int32_t *ticket;
     int32_t *err;                // [0] LC_BATCH_E_* bits, [1] 1 + largest malformed key
     int32_t err_base;            // that key's index in the caller's batch = err_base + key
-    uint32_t *lat_ws;            // unused (the 9-10-pending workspace is in LDS)
+    uint32_t *lat_ws;            // k_spec, k_spec_rerun: the waves' 9-10-pending workspaces in global
+                                 // memory (k_search_lattice keeps its own in LDS)
     const Args *full;            // device copy: results, counters, spill list
     uint64_t budget;
     int32_t n_order;
@@ -1289,8 +1290,12 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
                     status = 3;
                 } else {
                     if (RM < 16 && n == 8) {  // 9 pending: move the lattice to the workspace
+                        // (rows from one opaque lane column, as in spec_walk: a
+                        // workspace in global memory kept 30 VGPRs of row
+                        // addresses alive in k_spec_rerun otherwise)
+                        uint32_t *const mW = m.W + opq_lane(lane);
 #pragma unroll
-                        for (int k = 0; k < T0_RMEM; ++k) m.W[k * 64 + lane] = k < RM ? W[k < RM ? k : 0] : 0u;
+                        for (int k = 0; k < T0_RMEM; ++k) mW[k * 64] = k < RM ? W[k < RM ? k : 0] : 0u;
                         in_mem = true;
                     }
                     const Xfer x{(uint32_t)__builtin_amdgcn_readlane(xc.k, i),
@@ -1342,8 +1347,9 @@ __device__ __forceinline__ void lattice_walk(uint32_t (&W)[RM], LatWalk &out, co
                 }
                 live = r ? live : (1u << last) - 1u;
                 if (RM < 16 && in_mem && n == 9 && !r) {  // back to registers: no config holds index 8 or 9
+                    const uint32_t *const mW = m.W + opq_lane(lane);
 #pragma unroll
-                    for (int k = 0; k < RM; ++k) W[k] = m.W[k * 64 + lane];
+                    for (int k = 0; k < RM; ++k) W[k] = mW[k * 64];
                     in_mem = false;
                 }
                 n = r ? n : n - 1;
@@ -1413,8 +1419,9 @@ __device__ __forceinline__ int lattice_key(const T0Args &a, int32_t key, uint32_
     const Args &f = *a.full;
 
     if (!w.in_mem) {
+        uint32_t *const mW = m.W + opq_lane(lane);
 #pragma unroll
-        for (int k = 0; k < RM; ++k) m.W[k * 64 + lane] = W[k];
+        for (int k = 0; k < RM; ++k) mW[k * 64] = W[k];
     }
     if (!(a.flags & T0_DBG_NOFINAL)) write_final_mem(f, key, m, lane, w.slot_v, w.live);
     const uint32_t pr = __ockl_wfred_add_u32(w.probes);

@@ -50,9 +50,20 @@ struct StepPlan {
     bool side_validate = false;  // a validation kernel on the second stream, beside the register tier
     int spec_vblocks = 0;      // k_spec: validation blocks in its own launch
     bool spec_vfirst = false;  // ... ahead of the keys' blocks
+    int rerun_grid = 1;        // k_spec_rerun: its one-wave workgroups
     uint32_t t0_path = LC_T0_PATH_NONE;  // lc_stats.t0_path
     uint32_t ev_word_bytes = 0;          // lc_stats.ev_word_bytes
 };
+
+// One-wave workgroups of the rerun launch at most: the smallest of 8, 32 and
+// 128 at which the launch, beside the other lane's k_spec, takes what it takes
+// alone (all three did: 0.0044, 0.0047, 0.0050 ms against 0.0042; C2 the
+// same with each; profiles/rerun_thin.json).  A/B: make variant
+// VFLAGS=-DLC_SPEC_RERUN_GRID=n.
+#ifndef LC_SPEC_RERUN_GRID
+#define LC_SPEC_RERUN_GRID 8
+#endif
+constexpr int SPEC_RERUN_GRID = LC_SPEC_RERUN_GRID;
 
 inline StepPlan plan_step(const StepIn &in) {
     StepPlan p;
@@ -142,6 +153,12 @@ inline StepPlan plan_step(const StepIn &in) {
     p.side_validate = K > 0 && ((p.strict && !p.spec) || p.gen_validate);
     p.spec_vblocks = p.spec && p.strict ? (int)std::min<int64_t>(K, in.cu_count) : 0;
     p.spec_vfirst = p.spec && K * segs > (int64_t)in.cu_count * 16;
+    // The rerun launch (k_spec_rerun) is in every step and usually finds no
+    // key, so its dispatch is what it costs: a fixed number of one-wave
+    // workgroups, whatever the chip's size, that fit beside the other
+    // lane's k_spec blocks.  Wave b works in slot b of the step's K * segs
+    // k_spec workspaces, and more waves than keys would find nothing to do.
+    p.rerun_grid = (int)std::max<int64_t>(1, std::min<int64_t>(SPEC_RERUN_GRID, p.spec ? K : 1));
     return p;
 }
 
