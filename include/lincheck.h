@@ -972,7 +972,17 @@ void lc_perf_hist_free(lc_perf_hist *h);
  *     included.  Deferred keys are checked at finish with peaks and final
  *     configs requested;
  *   - lc_stream_report renders a key's counterexample from the stream itself.
- * LC_STREAM_EXACT with LC_STREAM_SET_TIER is refused (LC_E_UNSUPPORTED).
+ * LC_STREAM_EXACT with LC_STREAM_SET_TIER: the set that migrates is then
+ * Knossos's own, and so is every set of the set tier, so all of the above
+ * holds for a key in the set tier too: it turns :unknown / invalid at the
+ * oracle's event in the call that reaches it, with its peak and the final
+ * configs of the set before that event (the max_final smallest in slot-mask,
+ * state-id order), a live set-tier key reports its peak so far, and
+ * lc_stream_finish fetches its end set.  A key that falls back (a set past
+ * 32,768 configs that is still within the budget, window slot 56, a 256th
+ * state) gets its record at finish like any deferred key.  On a packer-only
+ * stream (ctx NULL), which has no set tier to make exact, the two flags
+ * together are refused (LC_E_UNSUPPORTED).
  * LC_OPT_COUNT_PROBES on the context is ignored by a stream, as without it. */
 typedef struct lc_stream lc_stream;  /* library-owned */
 

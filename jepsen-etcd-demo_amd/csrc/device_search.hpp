@@ -190,6 +190,25 @@ struct StreamSetArgs {
 hipError_t launch_stream_migrate(const StreamSetArgs &a, int grid, hipStream_t s);
 hipError_t launch_stream_set(const StreamSetArgs &a, int grid, hipStream_t s);
 
+// The exact set tier (LC_STREAM_EXACT | LC_STREAM_SET_TIER;
+// device_stream_set_exact.hip).  k_stream_set_exact is k_stream_set's search
+// over the same items, records and workspace with the oracle's accounting: set
+// sizes against `budget`, the running peak in the key's register record, and a
+// key that dies at an event (STREAM_INVALID, STREAM_BUDGET) leaves the
+// max_final smallest configs of the set before it in final_cfg / n_final.
+// k_stream_set_final writes them for set-tier keys still live at
+// lc_stream_finish: set.items[0 .. set.n_items) name the records (set_rec, key).
+struct StreamSetExactArgs {
+    StreamSetArgs set;
+    uint32_t *rec;            // the register records: STREAM_H_PEAK is read and written
+    uint64_t *final_cfg;      // [key][max_final][2] (stream_plan.hpp stream_final_off64)
+    uint32_t *n_final;        // [key]
+    uint64_t budget;
+    int32_t max_final;
+};
+hipError_t launch_stream_set_exact(const StreamSetExactArgs &a, int grid, hipStream_t s);
+hipError_t launch_stream_set_final(const StreamSetExactArgs &a, int grid, hipStream_t s);
+
 // Key segments (device_segments.hip): a register-tier step
 // whose keys are cut at quiescent points and searched as independent
 // segments, then composed per key.  Device arrays of seg_cap entries each

@@ -257,7 +257,18 @@ int push_enqueue(StreamDev *s, Dev *d, const Push &p, const PushLayout &l, size_
     // its set words -- each launch sees what the one before it stored
     if (p.n_mig) HIPCHK(lcd::launch_stream_migrate(sa, (int)std::min<int64_t>(p.n_mig, 8192), d->stream));
     if (p.sets) HIPCHK(hipEventRecord(s->ev[4], d->stream));
-    if (p.n_set) HIPCHK(lcd::launch_stream_set(sa, (int)std::min<int64_t>(p.n_set, s->set_ws_slots), d->stream));
+    if (p.n_set && s->exact) {  // the exact set tier: the same items, records and workspace
+        lcd::StreamSetExactArgs xs{};
+        xs.set = sa;
+        xs.rec = s->rec;
+        xs.final_cfg = s->fin;
+        xs.n_final = s->nfin;
+        xs.budget = s->ctx->o.max_configs;
+        xs.max_final = s->ctx->o.max_final;
+        HIPCHK(lcd::launch_stream_set_exact(xs, (int)std::min<int64_t>(p.n_set, s->set_ws_slots), d->stream));
+    } else if (p.n_set) {
+        HIPCHK(lcd::launch_stream_set(sa, (int)std::min<int64_t>(p.n_set, s->set_ws_slots), d->stream));
+    }
     if (p.sets) HIPCHK(hipEventRecord(s->ev[5], d->stream));
     HIPCHK(hipMemcpyAsync(s->hout, s->dout, head * 4, hipMemcpyDeviceToHost, d->stream));
     HIPCHK(hipEventRecord(s->ev[3], d->stream));
@@ -384,17 +395,38 @@ int lcst::stream_dev_peaks(StreamDev *s, int64_t n_keys, uint32_t *out) {
 }
 
 int lcst::stream_dev_finals(StreamDev *s, int64_t n_keys, const int32_t *keys, int64_t n_live, uint32_t init_state,
-                            uint64_t *cfg, uint32_t *n_final) {
+                            uint64_t *cfg, uint32_t *n_final, const SetLive *set_live, int64_t n_set_live) {
     if (!s->exact) return lc::fail(LC_E_INVALID, "lc_stream: final configs are kept in exact mode only");
     s->final_ms = 0;
     if (n_keys <= 0) return LC_OK;
     for (int64_t i = 0; i < n_live; ++i)
         if (keys[i] < 0 || keys[i] >= n_keys)
             return lc::fail(LC_E_INVALID, "lc_stream: live key %lld is out of range (internal error)", (long long)i);
+    for (int64_t i = 0; i < n_set_live; ++i)
+        if (set_live[i].key < 0 || set_live[i].key >= n_keys || !set_slot_ptr(s, set_live[i].slot))
+            return lc::fail(LC_E_INVALID, "lc_stream: live set-tier key %lld is out of range (internal error)", (long long)i);
     CtxCall x(s->ctx);
     LCCHK(x.enter());
-    LCCHK(stream_grow(s, x.d, n_keys, (size_t)n_live * 4, 0));
+    const size_t set_off = up16((size_t)std::max<int64_t>(n_live, 0) * 4);
+    LCCHK(stream_grow(s, x.d, n_keys, set_off + (size_t)std::max<int64_t>(n_set_live, 0) * sizeof(lcd::StreamSetItem), 0));
     const uint32_t mf = (uint32_t)s->ctx->o.max_final;
+    if (n_set_live > 0) {  // the set tier's live keys: one workgroup each, before the copies back
+        for (int64_t i = 0; i < n_set_live; ++i) {
+            lcd::StreamSetItem m{set_slot_ptr(s, set_live[i].slot), set_live[i].key, 0u, 0u, 0u, 0u, 0u};
+            std::memcpy(s->hin + set_off + (size_t)i * sizeof m, &m, sizeof m);
+        }
+        lcd::StreamSetExactArgs xs{};
+        xs.set.items = (const lcd::StreamSetItem *)(s->din + set_off);
+        xs.set.n_items = (int32_t)std::min<int64_t>(n_set_live, (int64_t)1 << 24);
+        xs.rec = s->rec;
+        xs.final_cfg = s->fin;
+        xs.n_final = s->nfin;
+        xs.budget = s->ctx->o.max_configs;
+        xs.max_final = (int32_t)mf;
+        HIPCHK(hipMemcpyAsync(s->din + set_off, s->hin + set_off, (size_t)n_set_live * sizeof(lcd::StreamSetItem),
+                              hipMemcpyHostToDevice, x.d->stream));
+        HIPCHK(lcd::launch_stream_set_final(xs, (int)std::min<int64_t>(n_set_live, 8192), x.d->stream));
+    }
     if (n_live > 0) {
         std::memcpy(s->hin, keys, (size_t)n_live * 4);
         lcd::StreamExactArgs a{};

@@ -64,8 +64,9 @@ void stream_dev_close(StreamDev *d);
 // joined behind lane 1) and return the keys that died, ascending by key.
 // n_keys: the stream's keys so far (records are grown, zero-filled, to hold them).
 // set (may be null): after k_stream, on the same lane, the migrations and then
-// one k_stream_set launch; keys that left the set tier are in `dead` too
-// (status STREAM_SET_FALLBACK for those that fell back).
+// one k_stream_set launch (exact mode: k_stream_set_exact, whose keys may also
+// die at the budget and leave their Final); keys that left the set tier are in
+// `dead` too (status STREAM_SET_FALLBACK for those that fell back).
 int stream_dev_push(StreamDev *d, int64_t n_keys, const Item *items, int64_t n_items, const uint16_t *ev16,
                     uint64_t n_ev, const uint32_t *trans, uint64_t n_trans, uint32_t init_state,
                     std::vector<Dead> *dead, const SetWork *set = nullptr, std::vector<Final> *fin = nullptr);
@@ -77,8 +78,13 @@ int stream_dev_push(StreamDev *d, int64_t n_keys, const Item *items, int64_t n_i
 // into the stream's arrays), then every key's configs and count back:
 // cfg[n_keys * max_final * 2], n_final[n_keys].
 int stream_dev_peaks(StreamDev *d, int64_t n_keys, uint32_t *out);
+// set_live (exact mode with the set tier): the set-tier keys still live, whose
+// end sets one k_stream_set_final launch writes before the copies back.
+struct SetLive {
+    int32_t key, slot;
+};
 int stream_dev_finals(StreamDev *d, int64_t n_keys, const int32_t *keys, int64_t n_live, uint32_t init_state,
-                      uint64_t *cfg, uint32_t *n_final);
+                      uint64_t *cfg, uint32_t *n_final, const SetLive *set_live = nullptr, int64_t n_set_live = 0);
 // Device time of the last stream_dev_finals launch, ms.
 double stream_dev_final_ms(const StreamDev *d);
 // The set-record pool: a slot for a migrating key (the pool is allocated on

@@ -31,6 +31,12 @@
 // key's (k_stream_final; deferred keys from the batch path), and
 // lc_stream_report renders a key's counterexample from the packer's own words
 // and rows (report_core.hpp).
+//
+// With both flags the set tier's launches are k_stream_set_exact's
+// (device_stream_set_exact.hip): the migrated set is Knossos's own, so a key
+// in the set tier dies at the budget or invalid at the oracle's event, with
+// its peak and final configs, and lc_stream_finish fetches the live set-tier
+// keys' too (k_stream_set_final).
 
 #include <algorithm>
 #include <chrono>
@@ -494,27 +500,32 @@ int check_mode(lc_stream *s, int mode, const char *fn) {
     return LC_OK;
 }
 
-// Exact mode at finish: the live register-tier keys' end sets (k_stream_final)
-// and every searched key's peak, into the keys.  Keys that died keep what
+// Exact mode at finish: the live register-tier keys' end sets (k_stream_final),
+// the live set-tier keys' (k_stream_set_final) and every searched key's peak,
+// into the keys.  Keys that died keep what
 // their launch left; deferred keys got theirs from the batch path.
 int finish_exact(lc_stream *s) {
     const size_t n = s->keys.size();
     if (!n) return LC_OK;
     std::vector<int32_t> live;
+    std::vector<lcst::SetLive> set_live;  // with the set tier: its keys still live (k_stream_set_final)
     for (size_t ki = 0; ki < n; ++ki) {
         const SKey &k = s->keys[ki];
-        if (!k.err && !k.dead && k.defer_at < 0) live.push_back((int32_t)ki);
+        if (k.err || k.dead) continue;
+        if (k.defer_at < 0) live.push_back((int32_t)ki);
+        else if (s->set_tier && !k.fell_back && k.set_slot >= 0) set_live.push_back(lcst::SetLive{(int32_t)ki, k.set_slot});
     }
     const size_t mf = (size_t)lcst::stream_dev_max_final(s->dev);
     std::vector<uint64_t> cfg(n * mf * 2 + 1);
     std::vector<uint32_t> n_final(n), peak(n);
     int rc = lcst::stream_dev_finals(s->dev, (int64_t)n, live.data(), (int64_t)live.size(), s->init_state, cfg.data(),
-                                     n_final.data());
+                                     n_final.data(), set_live.data(), (int64_t)set_live.size());
     if (rc) return rc;
     s->final_ms = lcst::stream_dev_final_ms(s->dev);
     s->final_keys = (int64_t)live.size();
     rc = lcst::stream_dev_peaks(s->dev, (int64_t)n, peak.data());
     if (rc) return rc;
+    for (const lcst::SetLive &sl : set_live) live.push_back(sl.key);
     for (int32_t ki : live) {
         SKey &k = s->keys[(size_t)ki];
         k.peak = peak[(size_t)ki];
@@ -546,9 +557,9 @@ extern "C" int lc_stream_open_opts(lc_ctx *ctx, const lc_pack_opts *opts, const 
     if (sopts && (sopts->flags & ~(uint32_t)(LC_STREAM_SET_TIER | LC_STREAM_EXACT)))
         return lc::fail(LC_E_INVALID, "lc_stream_open_opts: unknown flags 0x%x", sopts->flags);
     const bool exact = sopts && (sopts->flags & LC_STREAM_EXACT);
-    if (exact && (sopts->flags & LC_STREAM_SET_TIER))
-        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open_opts: LC_STREAM_EXACT with LC_STREAM_SET_TIER: the set tier keeps "
-                                          "no sizes and no final configs");
+    if (exact && (sopts->flags & LC_STREAM_SET_TIER) && !ctx)
+        return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open_opts: LC_STREAM_EXACT with LC_STREAM_SET_TIER: a packer-only "
+                                          "stream has no set tier to make exact");
     const int model = opts ? opts->model : LC_MODEL_CAS_REGISTER;
     if (model == LC_MODEL_MULTI_REGISTER)
         return lc::fail(LC_E_UNSUPPORTED, "lc_stream_open: multi-register has no register-tier search to resume");

@@ -148,4 +148,42 @@ constexpr bool stream_set_falls_back(uint64_t n_s, uint64_t n_i, uint32_t slot, 
     return n_s > STREAM_SET_CAP || n_i > STREAM_SET_CAP || slot >= STREAM_SET_MAX_SLOTS || states > STREAM_SET_MAX_STATES;
 }
 
+// ---- the exact set tier (LC_STREAM_EXACT | LC_STREAM_SET_TIER; device_stream_set_exact.hip)
+// An exact register record holds Knossos's own S, so the set that migrates is
+// S itself and every |I| and |S'| of k_stream_set's step is the oracle's.  The
+// set record keeps its layout and gains no word: the key's running peak stays
+// where k_stream_exact left it, in its register record's STREAM_H_PEAK -- the
+// register record is idle once the key has migrated -- and k_stream_set_exact
+// reads it before a key's new words and stores it after them, so
+// stream_dev_peaks and a dead key's Final read one place for both tiers.
+//
+// What an :ok at event e decides, in the oracle's order (table_full: a hash
+// set took no more entries; n_i = |I|, n_s = |S'|).  The kernel's counts are
+// exact while they are at most the cap; past it they only say "past the cap"
+// (an entry beyond an array's end leaves its hash set again and may be counted
+// twice, and the closure stops past stream_set_closure_stop), so the kernel
+// passes stream_set_exact_count of each.  A budget above the cap thus meets the
+// cap first: the key falls back and the batch path meets the budget.
+constexpr uint64_t stream_set_exact_count(uint64_t counted) {
+    return counted > STREAM_SET_CAP ? (uint64_t)STREAM_SET_CAP + 1 : counted;
+}
+constexpr uint32_t stream_set_exact_decide(bool table_full, uint64_t n_i, uint64_t n_s, uint64_t budget) {
+    return table_full                ? STREAM_ERROR
+           : n_i > budget            ? STREAM_BUDGET
+           : n_i > STREAM_SET_CAP    ? STREAM_SET_FALLBACK
+           : n_s == 0                ? STREAM_INVALID
+           : n_s > budget            ? STREAM_BUDGET
+           : n_s > STREAM_SET_CAP    ? STREAM_SET_FALLBACK
+                                     : STREAM_LIVE;
+}
+// |I| past which the closure need not go on: the decision is made either way.
+constexpr uint32_t stream_set_closure_stop(uint64_t budget) {
+    return budget < STREAM_SET_CAP ? (uint32_t)budget : STREAM_SET_CAP;
+}
+// Final configs of a set-tier key: the max_final smallest in (slot mask, state
+// id) order, write_final_mem's canonical choice.  A narrow config is
+// state << 56 | mask, so that order is the config's rotated left by 8 bits.
+constexpr uint64_t stream_set_sort_key(uint64_t cfg) { return cfg << 8 | cfg >> 56; }
+constexpr uint64_t stream_set_sort_key_cfg(uint64_t key) { return key >> 8 | key << 56; }
+
 }  // namespace lc

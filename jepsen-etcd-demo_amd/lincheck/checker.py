@@ -548,7 +548,8 @@ class Linearizable:
         rows are appended while the test runs and verdicts come back online.
         set_tier: keys past the register tier keep being searched online too.
         exact: the stream keeps Knossos's exact sets -- any :max-configs, peaks,
-        final configs and `Stream.analysis` online (not with set_tier).
+        final configs and `Stream.analysis` online; with set_tier as well, for
+        the keys in the set tier too.
         :algorithm :wgl has no resident search and raises."""
         from .stream import Stream
         if self.algorithm == N.LC_ALGO_WGL:

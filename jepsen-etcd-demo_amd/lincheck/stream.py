@@ -27,7 +27,11 @@ once, every key's after `finish`, equal to the one-shot check's -- and
 `Stream(dev, set_tier=True)` keeps a key that passes 10 pending ops or 32
 register values on the device too (the resident set tier): it is reported
 online like the others instead of at `finish`; `tiers()` / `key_tier(i)` say
-where each key is searched.
+where each key is searched.  With `exact=True` as well the set tier keeps the
+exact sets too: a key that is invalid, or past the budget, only after leaving
+the register tier is reported -- and `analysis` renders it -- in the append
+that reaches the event, and only keys whose sets pass 32,768 configs within
+the budget wait for `finish`.
 
 Models: cas-register, register and mutex.  (model/multi-register) and
 :algorithm :wgl have no register-tier search to resume and raise.
@@ -79,8 +83,10 @@ class Stream:
         """set_tier: a key that leaves the register tier (10 ops pending, 32
         states) migrates to the resident set tier and keeps being searched
         online, instead of waiting for `finish` (LC_STREAM_SET_TIER).
-        exact: the register tier keeps Knossos's exact sets (LC_STREAM_EXACT;
-        not together with set_tier)."""
+        exact: the register tier keeps Knossos's exact sets (LC_STREAM_EXACT).
+        Both: the set that migrates is exact too, so a key in the set tier
+        also meets any budget at the oracle's event and brings its peak and
+        final configs (a packer-only stream, dev None, refuses the pair)."""
         self.model = model if model is not None else CASRegister()
         if isinstance(self.model, MultiRegister):
             raise NotImplementedError("a stream checks (model/cas-register), (model/register) and (model/mutex)")

@@ -7,7 +7,12 @@
 // above 1 MB), mangled EDN text and Fressian bytes, and malformed op
 // sequences; and the streaming packer with lc_stream_report (a packer-only
 // LC_STREAM_EXACT stream fed in pieces, reports asked for while rows are still
-// held back).  Exit status 0 = every check passed and no sanitizer fired.
+// held back); and host_stream.cpp's paths behind a launch -- the dead list with
+// its Final entries for keys that die in the set tier, finish over live
+// set-tier keys, lc_stream_results and lc_stream_report for such keys -- on an
+// LC_STREAM_EXACT | LC_STREAM_SET_TIER stream whose device half is
+// stream_dev_stub.cpp's scripted stand-in (no GPU code runs here).
+// Exit status 0 = every check passed and no sanitizer fired.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -39,7 +44,11 @@ static int failures = 0;
         }                                                                          \
     } while (0)
 
+extern "C" lc_ctx *sanitize_fake_ctx();  // stream_dev_stub.cpp
+
 static void exercise_stream(const lc_history &h, int model);
+static void exercise_stream_set(const lc_history &h, int model);
+static int64_t set_tier_deaths = 0, set_tier_live_at_finish = 0, set_tier_fallen_back = 0;
 
 // pack, render every key's report, run the oracle; returns keys
 static int64_t exercise(const lc_history &h, int model, const int64_t *init = nullptr, int32_t n_init = 0) {
@@ -86,7 +95,10 @@ static int64_t exercise(const lc_history &h, int model, const int64_t *init = nu
     }
     const int64_t nk = b.n_keys;
     lc_packed_free(p);
-    if (!init && h.n <= 40000) exercise_stream(h, model);  // (the 3,000-key shape is for the EDN split)
+    if (!init && h.n <= 40000) {  // (the 3,000-key shape is for the EDN split)
+        exercise_stream(h, model);
+        exercise_stream_set(h, model);
+    }
     if (model == LC_MODEL_MULTI_REGISTER) return nk;  // the C oracle has no table models
     int64_t ok = oracle_check_history_model(&h, model, 1 << 14, 4, nullptr, nullptr, 0);
     if (ok > 0) {
@@ -149,6 +161,76 @@ static void exercise_stream(const lc_history &h, int model) {
     lc_stream_update u;
     CHECK(lc_stream_finish(s, &u) == LC_OK);
     reports();
+    lc_stream_close(s);
+}
+
+// The same history through an exact stream with the set tier on the stub's
+// scripted device, 97 rows per append: after every append and after finish the
+// whole record of every key (lc_stream_results with every array), and for each
+// key that is no longer valid its report from the configs the stream kept.
+static void exercise_stream_set(const lc_history &h, int model) {
+    lc_pack_opts po{model, 0, nullptr};
+    lc_stream_opts so{LC_STREAM_EXACT | LC_STREAM_SET_TIER};
+    lc_stream *s = nullptr;
+    CHECK(lc_stream_open_opts(nullptr, &po, &so, &s) == LC_E_UNSUPPORTED || model == LC_MODEL_MULTI_REGISTER);
+    if (lc_stream_open_opts(sanitize_fake_ctx(), &po, &so, &s) != LC_OK) return;  // (multi-register: no stream)
+    std::vector<int64_t> w(4096);
+    constexpr size_t MF = 10;  // the stub's max_final
+    auto records = [&](bool finished) {
+        const int64_t nk = lc_stream_keys(s, nullptr);
+        const size_t n = (size_t)std::max<int64_t>(nk, 1);
+        std::vector<int8_t> valid(n);
+        std::vector<int32_t> fev(n);
+        std::vector<uint8_t> cause(n);
+        std::vector<uint32_t> peak(n), n_final(n);
+        std::vector<uint64_t> fin(n * MF * 2);
+        lc_result r{};
+        r.valid = valid.data(); r.fail_event = fev.data(); r.cause = cause.data();
+        r.peak_configs = peak.data(); r.n_final = n_final.data(); r.final_configs = fin.data();
+        CHECK(lc_stream_results(s, &r) == LC_OK);
+        int64_t tiers[4];
+        CHECK(lc_stream_tiers(s, tiers) == LC_OK && tiers[0] + tiers[1] + tiers[2] + tiers[3] == nk);
+        for (int64_t i = 0; i < nk; ++i) {
+            CHECK(n_final[(size_t)i] <= MF);
+            const int tier = lc_stream_key_tier(s, i);
+            int64_t ev[4];
+            CHECK(lc_stream_key_events(s, i, ev) == LC_OK);
+            const bool past = ev[2] >= 0;  // it left the register tier
+            if (finished && past && tier == LC_STREAM_TIER_SET) { ++set_tier_live_at_finish; CHECK(n_final[(size_t)i] == 2); }
+            if (finished && tier == LC_STREAM_TIER_FALLEN_BACK) { ++set_tier_fallen_back; CHECK(peak[(size_t)i] == 3); }
+            if (lc_stream_key_error(s, i) || valid[(size_t)i] == LC_VALID) continue;
+            if (past && tier == LC_STREAM_TIER_DEAD) {
+                if (finished) ++set_tier_deaths;
+                CHECK(fev[(size_t)i] >= ev[2] && peak[(size_t)i] == 7 && n_final[(size_t)i] == 2);
+                CHECK(valid[(size_t)i] == (cause[(size_t)i] == LC_CAUSE_BUDGET ? LC_UNKNOWN : LC_INVALID));
+            }
+            const int64_t need = lc_stream_report(s, i, valid[(size_t)i], fev[(size_t)i], fin.data() + (size_t)i * MF * 2,
+                                                  n_final[(size_t)i], 10, w.data(), (int64_t)w.size());
+            CHECK(need >= 4);
+            if (need > (int64_t)w.size()) {
+                w.resize((size_t)need);
+                CHECK(lc_stream_report(s, i, valid[(size_t)i], fev[(size_t)i], fin.data() + (size_t)i * MF * 2, n_final[(size_t)i],
+                                       10, w.data(), need) == need);
+            }
+        }
+    };
+    for (int64_t lo = 0; lo < h.n; lo += 97) {
+        lc_history part = h;
+        part.n = std::min<int64_t>(97, h.n - lo);
+        part.type += lo; part.f += lo; part.process += lo; part.key += lo; part.v0 += lo; part.v1 += lo;
+        if (part.index) part.index += lo;
+        part.mop_off = part.mop = nullptr;
+        lc_stream_update u;
+        if (lc_stream_append(s, &part, &u) != LC_OK) break;
+        if (lo / 97 % 4 == 0) records(false);
+    }
+    lc_stream_update u;
+    CHECK(lc_stream_finish(s, &u) == LC_OK);
+    records(true);
+    double st[6];
+    CHECK(lc_stream_set_stats(s, st) == LC_OK);
+    int64_t tiers[4];
+    CHECK(lc_stream_tiers(s, tiers) == LC_OK && (int64_t)st[3] == tiers[LC_STREAM_TIER_SET]);  // slots in use: the live set keys'
     lc_stream_close(s);
 }
 
@@ -317,6 +399,10 @@ int main(int argc, char **argv) {
         exercise(h, LC_MODEL_MULTI_REGISTER, init, 2);
     }
     std::remove(tmp);
+    // the scripted device let keys die in the set tier, stay live there and fall back
+    CHECK(set_tier_deaths > 0 && set_tier_live_at_finish > 0 && set_tier_fallen_back > 0);
+    std::printf("set tier on the stub: %lld keys died there, %lld live at finish, %lld fell back\n",
+                (long long)set_tier_deaths, (long long)set_tier_live_at_finish, (long long)set_tier_fallen_back);
     std::printf("host sanitizer driver: %d failed checks\n", failures);
     return failures ? 1 : 0;
 }

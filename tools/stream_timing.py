@@ -13,6 +13,13 @@ Shapes:
       migrations and k_stream_set, the share of leaving keys that fall back,
       and the set-record pool's bytes.  --d-info-rate 0.05: the history whose
       sets grow past the cap.
+  (dx) shape (d) in three forms alternating in one process: set_tier alone,
+      exact alone (keys that leave the register tier restart at finish) and
+      both (the exact set tier): totals, finish, the register tier's kernel,
+      the migrations and k_stream_set / k_stream_set_exact device time.  With
+      --exact on|off --tree, shapes (a) and (b) against the parent commit's
+      tree give the register-only streams beside it
+      (profiles/stream_exact_set_timing.json).
 
 Per append: the host clock around the call, and the library's own split
 (lc_stream_last_timing): host packing, then device events around the upload,
@@ -251,6 +258,42 @@ def shape_d(dev, reps, info_rate):
     return out
 
 
+def shape_d_exact(dev, reps, info_rate):
+    """Shape (d) in three forms, alternating: the set tier alone, the exact mode
+    alone (keys that leave the register tier restart at finish) and both (the
+    exact set tier: k_stream_set_exact, k_stream_set_final at finish)."""
+    from lincheck import history as H
+    from lincheck.checker import Packed
+    h = H.synth(n_keys=100, ops_per_key=100, concurrency=10, interleave=True, nemesis_period=5.0, info_rate=info_rate,
+                anomaly_rate=0.1, seed=11 if info_rate == 0.02 else 12)
+    want = dev.check(Packed(h))  # with peaks and final configs: the exact forms' records are compared too
+    n_app = -(-len(h) // 100)
+    forms = {"set_tier": dict(set_tier=True), "exact": dict(exact=True), "exact_set_tier": dict(set_tier=True, exact=True)}
+    for kw in forms.values():  # warm-up of every form
+        run_stream(dev, h, n_app, want, **kw)
+    out = dict(shape="dx", rows=len(h), rows_per_append=100, info_rate=info_rate, forms={f: [] for f in forms})
+    for _ in range(reps):
+        for f, kw in forms.items():
+            run = run_stream(dev, h, n_app, want, **kw)
+            d = digest(run)
+            d["kernel_ms"]["sum"] = sum(p["kernel_ms"] for p in run["per_append"])
+            if kw.get("set_tier"):
+                for k in ("migrate_ms", "set_kernel_ms"):
+                    d[k] = summary(p[k] for p in run["per_append"])
+                    d[k]["sum"] = sum(p[k] for p in run["per_append"])
+                d.update({k: run[k] for k in ("tiers", "keys_left_register_tier", "fallback_share", "pool")})
+            if kw.get("exact"):
+                d["final_kernel_ms"], d["n_invalid"] = run["final_kernel_ms"], run["n_invalid"]
+            out["forms"][f].append(d)
+    for k in ("total_ms", "finish_ms"):
+        out[k] = {f: summary(x[k] for x in out["forms"][f]) for f in forms}
+    out["wall_per_append_ms"] = {f: summary(x["wall_ms"]["median"] for x in out["forms"][f]) for f in forms}
+    out["register_kernel_sum_ms"] = {f: summary(x["kernel_ms"]["sum"] for x in out["forms"][f]) for f in forms}
+    out["set_kernel_sum_ms"] = {f: summary(x["set_kernel_ms"]["sum"] for x in out["forms"][f]) for f in forms if "set_tier" in f}
+    out["migrate_sum_ms"] = {f: summary(x["migrate_ms"]["sum"] for x in out["forms"][f]) for f in forms if "set_tier" in f}
+    return out
+
+
 def shape_exact(dev, name, reps, on):
     """One form (exact on / off) of shape a, b (20 appends) or e."""
     import numpy as np
@@ -327,6 +370,8 @@ def main():
             doc["shapes"].append(shape_c(dev, a.reps))
         elif sh == "d":
             doc["shapes"].append(shape_d(dev, a.reps, a.d_info_rate))
+        elif sh == "dx":
+            doc["shapes"].append(shape_d_exact(dev, a.reps, a.d_info_rate))
         print(json.dumps({k: v for k, v in doc["shapes"][-1].items() if k != "forms"})[:2000], flush=True)
     if a.profile:
         try:
