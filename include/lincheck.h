@@ -153,7 +153,11 @@ typedef struct lc_history {
 #define LC_TABLE_NONE 0xFFFFu
 
 /* Limits of the packed form.  A key beyond them is reported :unknown with
- * cause LC_CAUSE_WINDOW / LC_CAUSE_STATES (identically in oracle/). */
+ * cause LC_CAUSE_WINDOW / LC_CAUSE_STATES (identically in oracle/).  With
+ * per-key tables (trans_off and key_states) a key whose key_states exceeds
+ * LC_WIDE_MAX_STATES is never stepped, and its descriptors may install
+ * LC_STATE_NONE (lc_pack numbers the surplus values so); the other keys of
+ * the batch are searched as usual. */
 #define LC_NARROW_MAX_SLOTS  56   /* u64 config: 8-bit state | 56 slot bits   */
 #define LC_NARROW_MAX_STATES 255
 #define LC_WIDE_MAX_SLOTS    112  /* 2 x u64 config                          */

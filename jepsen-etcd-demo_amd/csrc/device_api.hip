@@ -477,7 +477,13 @@ static int validate_batch(const lc_batch *b) {
             return lc::fail(LC_E_INVALID, "batch: a table model needs n_table, trans_off and key_states");
         return LC_OK;
     }
-    for (int64_t i = 0; i < b->n_trans; ++i) {
+    // Per-key tables with state counts: every install is checked against its
+    // key's key_states with the events (validate_events, or T0's validation
+    // on the device).  lc_pack gives the values past a key's LC_WIDE_MAX_STATES-th
+    // state the id LC_STATE_NONE; such a key is never stepped (LC_CAUSE_STATES),
+    // and the other keys of its batch are still searched.
+    const bool per_key = b->trans_off && b->key_states;
+    for (int64_t i = 0; i < b->n_trans && !per_key; ++i) {
         uint32_t d = b->trans[i];
         uint32_t f = d & 3u, bb = d >> 17;
         if ((f == LC_T_WRITE || f == LC_T_CAS) && bb >= LC_STATE_NONE)

@@ -160,3 +160,128 @@ def multi_register_history(seed: int, n_keys=50, n_ops=60, procs=5, regs=("x", "
     for i, op in enumerate(ops):
         op["index"] = i
     return ops
+
+
+def register_history(seed: int, n_keys=12, n_ops=60, procs=8, n_values=5, width=2.0, corrupt=0.2, p_info=0.0,
+                     p_write=0.5):
+    """(model/register) histories linearizable by construction: each op is a
+    read or a write of one of n_values values with a linearization point
+    inside its interval, applied there to the register's true value; a read
+    returns the truth (nil before the first write).  A crashed op (:info, with
+    probability p_info) retires its process; a crashed write takes effect with
+    probability 1/2.  A corrupted key has one completed read in its second half
+    return n_values, a value no op writes.  The register has n_values + 1
+    states (nil included) once every value has been written."""
+    rng = random.Random(seed)
+    values = list(range(n_values))
+    rows = []
+    for k in range(n_keys):
+        points = sorted(rng.uniform(0, n_ops * 1.0) for _ in range(n_ops))
+        truth = None
+        bad = rng.randrange(n_ops // 2, n_ops) if rng.random() < corrupt else -1
+        free_at = {p: -1e9 for p in range(procs)}
+        next_p = procs
+        corrupted = False
+        for i, t in enumerate(points):
+            f = "write" if rng.random() < p_write else "read"
+            cands = [p for p in free_at if free_at[p] < t]
+            p = rng.choice(cands) if cands else None
+            if p is None:
+                p = next_p; next_p += 1
+            inv = max(t - rng.uniform(0, width), free_at.get(p, -1e9) + 1e-3)
+            done = t + rng.uniform(0, width)
+            crashed = rng.random() < p_info
+            apply = not crashed or rng.random() < 0.5
+            if f == "write":
+                v = rng.choice(values)
+                if apply:
+                    truth = v
+                out = v
+            else:
+                v, out = None, truth
+                if bad >= 0 and i >= bad and not corrupted and not crashed:
+                    out = n_values  # a value no write installs: no crashed write can stand in for it
+                    corrupted = True
+            rows.append((inv, "invoke", f, k, p, v))
+            rows.append((done, "info" if crashed else "ok", f, k, p, v if crashed else out))
+            free_at[p] = float("inf") if crashed else done  # a crashed process is retired
+    rows.sort(key=lambda x: x[0])
+    ops = [{"type": ty, "f": f, "value": Tuple(k, v), "process": 1000 * k + p} for _t, ty, f, k, p, v in rows]
+    for i, op in enumerate(ops):
+        op["index"] = i
+    return ops
+
+
+def mutex_crash_history(seed: int, n_keys=12, rounds=30, procs=6, width=2.0, corrupt=0.2, p_info=0.1, tail=4):
+    """(model/mutex) histories with crashed acquires and releases,
+    linearizable by construction.  Each round a process acquires at a
+    lock-free time t and the lock is released at t + hold, every op's interval
+    containing its linearization point.  An op crashes with probability p_info
+    (:info, its process retired) and then takes effect with probability 1/2:
+      * a crashed acquire that took effect is followed by a release from
+        another process (the model's lock has no owner); one that did not
+        leaves the lock free and the round ends there;
+      * a crashed release that took effect frees the lock; after one that did
+        not the lock is held for good, and only crashed ops (none of which
+        takes effect) follow, `tail` of them at the most, before the key ends.
+    A corrupted key loses every release that follows a completed acquire from
+    some round on: each later acquire then needs a crashed release to stand in
+    for a lost one, and the key is invalid once they run out."""
+    rng = random.Random(seed)
+    rows = []
+    for k in range(n_keys):
+        t = 0.0
+        free_at = {p: -1e9 for p in range(procs)}
+        next_p = [procs]
+        drop = rng.randrange(2, rounds) if rng.random() < corrupt else rounds
+
+        def proc(at):
+            cands = [p for p in free_at if free_at[p] < at - width]
+            if cands:
+                return rng.choice(cands)
+            next_p[0] += 1
+            free_at[next_p[0] - 1] = -1e9
+            return next_p[0] - 1
+
+        def op(f, lin, p, lo, hi):
+            """One op of process p linearized at lin, acknowledged within
+            (lin, lin + hi]: (crashed, took effect, time of its completion)."""
+            inv = max(lin - rng.uniform(0, width), free_at[p] + 1e-3, lo)
+            inv = min(inv, lin)
+            done = lin + rng.uniform(0, hi)
+            crashed = rng.random() < p_info
+            applied = not crashed or rng.random() < 0.5
+            rows.append((inv, "invoke", f, k, p))
+            rows.append((done, "info" if crashed else "ok", f, k, p))
+            free_at[p] = float("inf") if crashed else done
+            return crashed, applied, done
+
+        stuck = False
+        for r in range(rounds):
+            hold = rng.uniform(0.5, 2.0)
+            p = proc(t)
+            crashed, applied, a_done = op("acquire", t, p, -1e9, min(width, hold) * 0.9)
+            if applied:
+                q = p if not crashed else proc(t + hold)
+                if r >= drop and not crashed:
+                    pass  # the release is lost: the lock stays held as far as the history tells
+                else:
+                    crashed, applied, _ = op("release", t + hold, q, a_done + 1e-3, width)
+                    if not applied:
+                        stuck = True
+            t += hold + rng.uniform(0.01, 0.5)
+            if stuck:
+                break
+        if stuck:  # held for good: crashed ops only, none takes effect
+            for _ in range(rng.randint(0, tail)):
+                p = proc(t)
+                inv = max(t - rng.uniform(0, width), free_at[p] + 1e-3)
+                rows.append((inv, "invoke", rng.choice(["acquire", "release"]), k, p))
+                rows.append((t + rng.uniform(0, width), "info", rows[-1][2], k, p))
+                free_at[p] = float("inf")
+                t += rng.uniform(0.01, 0.5)
+    rows.sort(key=lambda x: x[0])
+    ops = [{"type": ty, "f": f, "value": Tuple(k, None), "process": 1000 * k + p} for _t, ty, f, k, p in rows]
+    for i, op_ in enumerate(ops):
+        op_["index"] = i
+    return ops
