@@ -775,6 +775,164 @@ int  lc_edn_parse_set(const char *text, int64_t len, lc_set_hist **out);
 int  lc_set_hist_view(const lc_set_hist *h, lc_set_history *out);
 void lc_set_hist_free(lc_set_hist *h);
 
+/* ---- checker/set-full (per-element set analysis; ABI 13, additive) ------------- */
+/* (checker/set-full {:linearizable? ...}) examines EVERY :ok :read, not only
+ * the last one, and classifies every element :stable, :lost or :never-read,
+ * with stable / lost latencies and the stale elements.  Restated from memory
+ * of the public Jepsen 0.2.x source of jepsen.checker/set-full; the rules
+ * below are this library's definition (parity
+ * unpinned).  Its own structs and entry points; nothing above changes.
+ *
+ * One key's (unwrapped) ops are folded in history order.  An op's POSITION is
+ * its row number in the history; comparisons use positions.  Rows whose
+ * :process is not an integer (LC_NO_PROCESS) are skipped.  State: elements
+ * (element -> {known, last-present, last-absent}, all nil), reads (process ->
+ * its open :read invocation), dups (element -> count).
+ *   :invoke :add v   elements[v] = a FRESH record (a second invocation of the
+ *                    same element discards what was known)
+ *   :ok :add v       known = known or this op; :fail / :info adds change nothing
+ *   :invoke :read    reads[p] = op; :fail :read removes reads[p]; :info: nothing
+ *   :ok :read V by p (nil = the empty collection) with inv = reads[p]: every x
+ *                    occurring c > 1 times in V sets dups[x] = max(dups[x], c)
+ *                    (untracked elements too); for EVERY element tracked at
+ *                    this moment: in V -> known = known or this op, and
+ *                    last-present = inv if last-present is nil or older
+ *                    (by position) than inv; else last-absent = inv likewise
+ * Errors (that key {:valid? :unknown :error ...}): an :ok :add with no earlier
+ * :invoke :add of its element; an :ok :read by a process with no open read; a
+ * nil or non-integer element (of an :invoke / :ok :add or inside an :ok :read);
+ * an :ok :read value that is neither nil nor a collection.
+ * Per element, idx(x) = x's position or -1 for nil:
+ *   stable?  last-present and idx(last-absent) < idx(last-present)
+ *   lost?    known and last-absent and idx(last-present) < idx(last-absent)
+ *            and idx(known) < idx(last-absent);       otherwise never-read
+ *   stable-latency = max(0, (last-absent ? last-absent.time + 1 : 0) - known.time) / 10^6
+ *   lost-latency   = max(0, (last-present ? last-present.time + 1 : 0) - known.time) / 10^6
+ *   (integer nanoseconds in, integer division, milliseconds out)
+ * :valid? by the first rule that fires: false if any element is lost; :unknown
+ * if none is stable; false if linearizable and any stable element has a
+ * stable-latency > 0 (is stale); else true -- and after that false if any
+ * element was duplicated in one read. */
+
+/* lc_set_history's columns plus :process and :time. */
+typedef struct lc_setfull_history {
+    int64_t        n;
+    const uint8_t *type;      /* LC_INVOKE / LC_OK_T / LC_FAIL / LC_INFO */
+    const uint8_t *f;         /* LC_SF_*                                  */
+    const int64_t *key;       /* or NULL                                  */
+    const int64_t *elem;
+    const int64_t *read_off;  /* [n + 1], or NULL */
+    const int64_t *read_elem;
+    const int64_t *index;     /* or NULL */
+    const int64_t *process;   /* LC_NO_PROCESS: not an integer (the row is skipped) */
+    const int64_t *time;      /* :time, ns; NULL: all 0 */
+} lc_setfull_history;
+
+#define LC_SETFULL_NONE (-1)  /* no such op (a position) */
+/* outcome of an id */
+#define LC_SETFULL_UNTRACKED  0  /* an id nobody invoked (a hole of an offset key, or only ever read) */
+#define LC_SETFULL_STABLE     1
+#define LC_SETFULL_LOST       2
+#define LC_SETFULL_NEVER_READ 3
+
+/*
+ * A packed set-full batch: lc_setfull_pack's output or caller-built.  Key k's
+ * elements are numbered by ids below span[k] exactly as in lc_set_batch
+ * (min / rank / vals_off / vals; csrc/set_plan.hpp: plan_set_key).  Every
+ * value of any :ok :read has an id too, invoked or not, so that a duplicate of
+ * an element nobody added is seen.  Key k's ids are id_off[k] .. id_off[k] +
+ * span[k] of the per-id arrays; its :ok reads, IN COMPLETION ORDER (history
+ * order, positions ascending), are rows row_off[k] .. row_off[k + 1]; row r's
+ * ids are read_id[el_off[r] .. el_off[r + 1]).  Keys whose status is not
+ * LC_SET_KEY_OK have no ids and no rows.  lc_setfull_check validates the
+ * offsets and the rows' order on the host; every id is checked against
+ * span[k] on the device, and a bad one ends the call with LC_E_INVALID naming
+ * the key.
+ */
+typedef struct lc_setfull_batch {
+    int64_t         n_keys;
+    const uint64_t *id_off;    /* [n_keys + 1]: id_off[k + 1] - id_off[k] >= span[k] */
+    const uint32_t *span;      /* [n_keys] */
+    const int64_t  *min;       /* [n_keys] */
+    const uint8_t  *rank;      /* [n_keys] */
+    const uint64_t *vals_off;  /* [n_keys + 1] */
+    const int64_t  *vals;
+    const uint8_t  *status;    /* [n_keys] LC_SET_KEY_OK / LC_SET_KEY_ERROR, or NULL: all OK */
+    /* per id */
+    const int64_t  *inv_pos;   /* position of the last :invoke :add, or LC_SETFULL_NONE (untracked) */
+    const int64_t  *ack_pos;   /* position of the first :ok :add after it, or LC_SETFULL_NONE */
+    const int64_t  *ack_time;  /* that op's :time */
+    /* per row (an :ok :read) */
+    const uint64_t *row_off;   /* [n_keys + 1] */
+    const int64_t  *row_pos;   /* the :ok's position: ascending inside a key */
+    const int64_t  *row_time;
+    const int64_t  *row_inv_pos;   /* its invocation's position (< row_pos) and :time */
+    const int64_t  *row_inv_time;
+    const uint64_t *el_off;    /* [rows + 1] into read_id, ascending from 0 */
+    const uint32_t *read_id;
+} lc_setfull_batch;
+
+typedef struct lc_setfull_packed lc_setfull_packed;  /* library-owned */
+
+/* independent/checker's split by key (keys in order of first appearance; one
+ * key LC_NO_KEY when no row has one), reads paired with their invocations by
+ * process, elements interned, the error rules applied per key. */
+int  lc_setfull_pack(const lc_setfull_history *h, lc_setfull_packed **out);
+void lc_setfull_packed_free(lc_setfull_packed *p);
+int  lc_setfull_packed_view(const lc_setfull_packed *p, lc_setfull_batch *out);
+int  lc_setfull_packed_keys(const lc_setfull_packed *p, int64_t *out);
+/* Why key i is :unknown (NULL when it is checked; borrowed). */
+const char *lc_setfull_packed_key_error(const lc_setfull_packed *p, int64_t i);
+
+#define LC_SETFULL_MARK_DIRECT 0x1u  /* k_setfull_mark's bits leave by the lanes' own atomics, no LDS tile (A/B) */
+typedef struct lc_setfull_opts {
+    int32_t  linearizable;      /* {:linearizable? true}: a stale element makes the key invalid */
+    uint32_t flags;             /* LC_SETFULL_* path flags (tests, A/B)                         */
+    uint64_t max_matrix_bytes;  /* most bytes of presence matrix per pass; 0: the default
+                                   (csrc/setfull_plan.hpp)                                      */
+} lc_setfull_opts;
+
+/*
+ * Per key: valid and six counts -- attempt (tracked ids), stable, lost,
+ * never-read, stale, duplicated.  Per id (the batch's id numbering, id_off[k]
+ * + id): outcome, the latency in ms (stable-latency of a stable id,
+ * lost-latency of a lost one, else -1), the positions of known and
+ * last-absent (LC_SETFULL_NONE for nil), and whether some read held it twice.
+ * Caller-allocated; n_ids = id_off[n_keys].
+ */
+typedef struct lc_setfull_result {
+    int8_t   *valid;        /* [n_keys] LC_VALID / LC_INVALID / LC_UNKNOWN */
+    uint64_t *counts;       /* [6 * n_keys] */
+    uint8_t  *outcome;      /* [n_ids] LC_SETFULL_*  */
+    int64_t  *latency;      /* [n_ids] */
+    int64_t  *known;        /* [n_ids] */
+    int64_t  *last_absent;  /* [n_ids] */
+    uint8_t  *duplicated;   /* [n_ids] 0 / 1 */
+} lc_setfull_result;
+
+/* Check every key of the batch in one call on the context's stream (first
+ * device of the context): H2D, per pass mark and scan, finish, D2H. */
+int  lc_setfull_check(lc_ctx *ctx, const lc_setfull_batch *b, const lc_setfull_opts *o, lc_setfull_result *r);
+/* Device-event times of the last lc_setfull_check, ms: [0] upload, [1] the
+ * mark kernels (all passes), [2] the scan and finish kernels, [3] download,
+ * [4] the whole call (wall), [5] the matrices' zeroing; then [6] passes and
+ * [7] matrix bytes zeroed in all. */
+int  lc_setfull_last_timing(lc_ctx *ctx, double *out8);
+/* Launch constants (no device needed): [0] ids of one wave of k_setfull_scan,
+ * [1] of one workgroup (bands are multiples of it), [2] read elements per
+ * workgroup of k_setfull_mark, [3] per lane (16-byte loads of four),
+ * [4] the ids of mark's LDS tile, [5] the default max_matrix_bytes. */
+int  lc_setfull_launch_info(int64_t *out6);
+
+/* history.edn of a set-workload run as lc_edn_read_set reads it (the same op
+ * handler), keeping :process (LC_NO_PROCESS when not an integer) and :time
+ * (0 when absent). */
+typedef struct lc_setfull_hist lc_setfull_hist;  /* library-owned */
+int  lc_edn_read_setfull(const char *path, lc_setfull_hist **out);
+int  lc_edn_parse_setfull(const char *text, int64_t len, lc_setfull_hist **out);
+int  lc_setfull_hist_view(const lc_setfull_hist *h, lc_setfull_history *out);
+void lc_setfull_hist_free(lc_setfull_hist *h);
+
 /* ---- checker/perf (etcdemo.clj:165-167, ABI 13) -------------------------------- */
 /* The demo's check phase is (checker/compose {:perf (checker/perf) :indep ...}).
  * This path computes what jepsen.checker.perf computes before it draws: the

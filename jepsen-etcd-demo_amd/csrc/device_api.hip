@@ -1755,6 +1755,21 @@ extern "C" int lc_set_last_timing(lc_ctx *c, double *out_ms) {
     return lcs::set_last_timing(c->dev[0]->setdev, out_ms);
 }
 
+// ---- checker/set-full (device_setfull.hip) -----------------------------------
+
+extern "C" int lc_setfull_check(lc_ctx *c, const lc_setfull_batch *b, const lc_setfull_opts *o, lc_setfull_result *r) {
+    if (!c || !b || !o || !r) return lc::fail(LC_E_INVALID, "lc_setfull_check: null argument");
+    CtxCall x(c);
+    LCCHK(x.enter());
+    return lcf::setfull_check(&x.d->setfulldev, x.d->stream, b, o, r);
+}
+
+extern "C" int lc_setfull_last_timing(lc_ctx *c, double *out8) {
+    if (!c || !out8) return lc::fail(LC_E_INVALID, "lc_setfull_last_timing: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    return lcf::setfull_last_timing(c->dev[0]->setfulldev, out8);
+}
+
 // ---- checker/perf (etcdemo.clj:165-167; device_perf.hip) ----------------------
 
 extern "C" int lc_perf_check(lc_ctx *c, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r) {

@@ -14,6 +14,7 @@
 #include "device_search.hpp"
 #include "device_perf.hpp"
 #include "device_set.hpp"
+#include "device_setfull.hpp"
 #include "step_plan.hpp"
 #include "lane_plan.hpp"
 
@@ -284,12 +285,14 @@ struct Dev {
     uint8_t *analyzer = nullptr;  // [cap_keys] LC_ALGO_* that answered each key
     lcs::SetDev *setdev = nullptr;  // lc_set_check's cached arrays (device_set.hip), made on first use
     lcp::PerfDev *perfdev = nullptr;  // lc_perf_check's (device_perf.hip), likewise
+    lcf::SetFullDev *setfulldev = nullptr;  // lc_setfull_check's (device_setfull.hip), likewise
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
         if (stream1) (void)hipStreamSynchronize(stream1);
         lcs::set_dev_free(setdev);
         lcp::perf_dev_free(perfdev);
+        lcf::setfull_dev_free(setfulldev);
         dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
         dfree(peak); dfree(final_cfg); dfree(n_final);

@@ -1131,3 +1131,100 @@ extern "C" const char *lc_perf_hist_name(const lc_perf_hist *h, int64_t i) {
 }
 
 extern "C" void lc_perf_hist_free(lc_perf_hist *h) { delete h; }
+
+// ---- history.edn for checker/set-full (ABI 13, additive) -------------------------
+// The set reader's op handler decides everything it decides for lc_edn_read_set
+// (parse_set above: client ops, tuples, elements); a second walk over the same
+// text with the reader keeps every op map's :process (LC_NO_PROCESS when it is
+// no integer) and :time (0 when absent or no integer).  Single-threaded.
+
+struct lc_setfull_hist {
+    lc_set_hist *base = nullptr;
+    std::vector<int64_t> process, time;
+    ~lc_setfull_hist() { delete base; }
+};
+
+namespace {
+
+bool read_setfull_meta(Parser &ps, lc_setfull_hist &h) {
+    ++ps.p;  // at '{'
+    int64_t process = LC_NO_PROCESS, time = 0;
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated op map");
+        if (*ps.p == '}') { ++ps.p; break; }
+        std::string_view k;
+        bool is_kw = false;
+        if (!ps.keyword(k, is_kw)) return false;
+        const uint64_t k8 = is_kw ? pack8(k) : 0;
+        if (is_kw && (k8 == P8("process") || k8 == P8("time"))) {
+            Leaf v;
+            if (!ps.shaped(v)) return false;
+            if (k8 == P8("process")) process = v.kind == K_INT ? v.i : LC_NO_PROCESS;
+            else time = v.kind == K_INT ? v.i : 0;
+        } else {
+            if (!ps.skip()) return false;
+        }
+    }
+    h.process.push_back(process);
+    h.time.push_back(time);
+    return true;
+}
+
+int parse_setfull(const char *text, int64_t len, lc_setfull_hist **out) {
+    auto h = std::make_unique<lc_setfull_hist>();
+    if (int rc = parse_set(text, len, &h->base)) return rc;
+    Parser ps{text, text + len, text};
+    for (;;) {  // the text parsed once already: op maps, bare or in one vector
+        ps.ws();
+        if (ps.p >= ps.end) break;
+        if (*ps.p == '[' || *ps.p == ']') { ++ps.p; continue; }
+        if (*ps.p != '{' || !read_setfull_meta(ps, *h)) break;
+    }
+    if (!ps.err.empty() || h->process.size() != h->base->type.size())
+        return lc::fail(LC_E_PARSE, "lc_edn_setfull: line %lld: %s", (long long)line_of(text, ps.err_off),
+                        ps.err.empty() ? "op maps differ between the two walks" : ps.err.c_str());
+    *out = h.release();
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_edn_parse_setfull(const char *text, int64_t len, lc_setfull_hist **out) {
+    lc::Range range("lc_edn_parse_setfull");
+    if (!text || !out || len < 0) return lc::fail(LC_E_INVALID, "lc_edn_parse_setfull: null argument");
+    try {
+        return parse_setfull(text, len, out);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_edn_setfull: out of memory");
+    }
+}
+
+extern "C" int lc_edn_read_setfull(const char *path, lc_setfull_hist **out) {
+    if (!path || !out) return lc::fail(LC_E_INVALID, "lc_edn_read_setfull: null argument");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return lc::fail(LC_E_IO, "lc_edn_read_setfull: cannot open %s", path);
+    std::string s;
+    try {
+        char buf[1 << 16];
+        size_t r;
+        while ((r = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, r);
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return lc::fail(LC_E_NOMEM, "lc_edn_read_setfull: out of memory");
+    }
+    std::fclose(f);
+    return lc_edn_parse_setfull(s.data(), (int64_t)s.size(), out);
+}
+
+extern "C" int lc_setfull_hist_view(const lc_setfull_hist *h, lc_setfull_history *out) {
+    if (!h || !out) return lc::fail(LC_E_INVALID, "lc_setfull_hist_view: null argument");
+    const lc_set_hist *b = h->base;
+    out->n = (int64_t)b->type.size();
+    out->type = b->type.data(); out->f = b->f.data(); out->key = b->key.data(); out->elem = b->elem.data();
+    out->read_off = b->read_off.data(); out->read_elem = b->read_elem.data(); out->index = b->index.data();
+    out->process = h->process.data(); out->time = h->time.data();
+    return LC_OK;
+}
+
+extern "C" void lc_setfull_hist_free(lc_setfull_hist *h) { delete h; }

@@ -137,6 +137,37 @@ class LcSetResult(C.Structure):
                 ("runs", P(C.c_int64)), ("run_cap", C.c_uint64), ("n_runs", C.c_uint64)]
 
 
+# ---- checker/set-full (ABI 13, additive) ----------------------------------------
+LC_SETFULL_NONE = -1
+LC_SETFULL_UNTRACKED, LC_SETFULL_STABLE, LC_SETFULL_LOST, LC_SETFULL_NEVER_READ = 0, 1, 2, 3
+LC_SETFULL_MARK_DIRECT = 0x1  # lc_setfull_opts.flags
+
+
+class LcSetFullHistory(C.Structure):
+    _fields_ = [("n", C.c_int64), ("type", P(C.c_uint8)), ("f", P(C.c_uint8)), ("key", P(C.c_int64)),
+                ("elem", P(C.c_int64)), ("read_off", P(C.c_int64)), ("read_elem", P(C.c_int64)),
+                ("index", P(C.c_int64)), ("process", P(C.c_int64)), ("time", P(C.c_int64))]
+
+
+class LcSetFullBatch(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("id_off", P(C.c_uint64)), ("span", P(C.c_uint32)), ("min", P(C.c_int64)),
+                ("rank", P(C.c_uint8)), ("vals_off", P(C.c_uint64)), ("vals", P(C.c_int64)), ("status", P(C.c_uint8)),
+                ("inv_pos", P(C.c_int64)), ("ack_pos", P(C.c_int64)), ("ack_time", P(C.c_int64)),
+                ("row_off", P(C.c_uint64)), ("row_pos", P(C.c_int64)), ("row_time", P(C.c_int64)),
+                ("row_inv_pos", P(C.c_int64)), ("row_inv_time", P(C.c_int64)), ("el_off", P(C.c_uint64)),
+                ("read_id", P(C.c_uint32))]
+
+
+class LcSetFullOpts(C.Structure):
+    _fields_ = [("linearizable", C.c_int32), ("flags", C.c_uint32), ("max_matrix_bytes", C.c_uint64)]
+
+
+class LcSetFullResult(C.Structure):
+    _fields_ = [("valid", P(C.c_int8)), ("counts", P(C.c_uint64)), ("outcome", P(C.c_uint8)),
+                ("latency", P(C.c_int64)), ("known", P(C.c_int64)), ("last_absent", P(C.c_int64)),
+                ("duplicated", P(C.c_uint8))]
+
+
 # ---- checker/perf (ABI 13) ---------------------------------------------------
 LC_PERF_MAX_F, LC_PERF_MAX_Q = 32, 8
 LC_PERF_NO_INVOKE = LC_NIL
@@ -246,6 +277,18 @@ SIGNATURES = {
     "lc_edn_parse_set": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
     "lc_set_hist_view": (C.c_int, [C.c_void_p, P(LcSetHistory)]),
     "lc_set_hist_free": (None, [C.c_void_p]),
+    "lc_setfull_pack": (C.c_int, [P(LcSetFullHistory), P(C.c_void_p)]),
+    "lc_setfull_packed_free": (None, [C.c_void_p]),
+    "lc_setfull_packed_view": (C.c_int, [C.c_void_p, P(LcSetFullBatch)]),
+    "lc_setfull_packed_keys": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_setfull_packed_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_setfull_check": (C.c_int, [C.c_void_p, P(LcSetFullBatch), P(LcSetFullOpts), P(LcSetFullResult)]),
+    "lc_setfull_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_setfull_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_edn_read_setfull": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+    "lc_edn_parse_setfull": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
+    "lc_setfull_hist_view": (C.c_int, [C.c_void_p, P(LcSetFullHistory)]),
+    "lc_setfull_hist_free": (None, [C.c_void_p]),
     "lc_perf_pack": (C.c_int, [P(LcPerfHistory), P(C.c_void_p)]),
     "lc_perf_packed_free": (None, [C.c_void_p]),
     "lc_perf_packed_view": (C.c_int, [C.c_void_p, P(LcPerfBatch)]),

@@ -11,6 +11,9 @@
     set_() (alias: set)
         jepsen.checker/set (set.clj:46), the set workload's checker:
         lincheck.setcheck.
+    set_full({"linearizable?": ...})
+        jepsen.checker/set-full: every read examined, every element :stable,
+        :lost or :never-read, with latencies and stale elements: lincheck.setfull.
     perf()
         jepsen.checker/perf (etcdemo.clj:166): always valid; the latency and
         rate series computed on the device: lincheck.perf.
@@ -759,6 +762,13 @@ def set_(opts: Optional[Dict] = None):
 globals()["set"] = set_
 
 
+def set_full(opts: Optional[Dict] = None):
+    """jepsen.checker/set-full: the per-element set analysis on the device
+    (lincheck.setfull).  opts: {"linearizable?": bool}."""
+    from .setfull import SetFullChecker
+    return SetFullChecker(opts)
+
+
 def perf(opts: Optional[Dict] = None):
     """jepsen.checker/perf (etcdemo.clj:166): {"valid?": True}; the series it
     would plot are computed on the device (lincheck.perf)."""
@@ -767,12 +777,13 @@ def perf(opts: Optional[Dict] = None):
 
 
 def batched_set(inner):
-    """The SetChecker inside `inner` if independent.checker can batch it."""
+    """The SetChecker (or SetFullChecker) inside `inner` if independent.checker can batch it."""
     from .setcheck import SetChecker
-    if isinstance(inner, SetChecker):
+    from .setfull import SetFullChecker
+    if isinstance(inner, (SetChecker, SetFullChecker)):
         return inner
     if isinstance(inner, Compose):
-        sets = [c for c in inner.checkers.values() if isinstance(c, SetChecker)]
+        sets = [c for c in inner.checkers.values() if isinstance(c, (SetChecker, SetFullChecker))]
         if len(sets) == 1 and not any(isinstance(c, Linearizable) for c in inner.checkers.values()):
             return sets[0]
     return None
