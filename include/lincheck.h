@@ -933,6 +933,13 @@ int  lc_edn_parse_setfull(const char *text, int64_t len, lc_setfull_hist **out);
 int  lc_setfull_hist_view(const lc_setfull_hist *h, lc_setfull_history *out);
 void lc_setfull_hist_free(lc_setfull_hist *h);
 
+/* ---- streaming checker/set-full (ABI 13, additive) ------------------------------ */
+/* Per-element verdicts while the set test runs: a stream that rows are appended
+ * to, whose results after every append are those of the two calls above on
+ * everything appended so far.  Its structs and entry points are this header's
+ * next section, kept in a file of its own: include/lincheck_setfull_stream.h
+ * (DESIGN.md section 3.13), exported by the same library. */
+
 /* ---- checker/perf (etcdemo.clj:165-167, ABI 13) -------------------------------- */
 /* The demo's check phase is (checker/compose {:perf (checker/perf) :indep ...}).
  * This path computes what jepsen.checker.perf computes before it draws: the

@@ -329,6 +329,40 @@ SIGNATURES = {
     "lc_stream_close": (None, [C.c_void_p]),
 }
 
+
+# ---- streaming set-full (include/lincheck_setfull_stream.h; ABI 13, additive) ----
+# A header and a table of their own: SIGNATURES mirrors include/lincheck.h name for name.
+LC_SFS_FRESH, LC_SFS_ACK = 0x1, 0x2  # lc_setfull_stream_chunk.en_flags
+
+
+class LcSetFullStreamUpdate(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("rows", C.c_int64), ("reads", C.c_int64), ("ids", C.c_int64),
+                ("n_changed", C.c_int64), ("changed", P(C.c_int64))]
+
+
+class LcSetFullStreamChunk(C.Structure):
+    _fields_ = [("n_touched", C.c_int64), ("tk_key", P(C.c_int64)), ("tk_n_ids", P(C.c_uint32)),
+                ("tk_row_off", P(C.c_uint64)), ("tk_blk_off", P(C.c_uint64)), ("blk", P(C.c_uint32)),
+                ("n_entries", C.c_int64), ("en_t", P(C.c_uint32)), ("en_id", P(C.c_uint32)), ("en_flags", P(C.c_uint32)),
+                ("en_inv_pos", P(C.c_int64)), ("en_ack_pos", P(C.c_int64)), ("en_ack_time", P(C.c_int64)),
+                ("row_pos", P(C.c_int64)), ("row_time", P(C.c_int64)), ("row_inv_pos", P(C.c_int64)),
+                ("row_inv_time", P(C.c_int64)), ("el_off", P(C.c_uint64)), ("read_id", P(C.c_uint32))]
+
+
+SETFULL_STREAM_SIGNATURES = {
+    "lc_setfull_stream_open": (C.c_int, [C.c_void_p, P(LcSetFullOpts), P(C.c_void_p)]),
+    "lc_setfull_stream_append": (C.c_int, [C.c_void_p, P(LcSetFullHistory), P(LcSetFullStreamUpdate)]),
+    "lc_setfull_stream_counts": (C.c_int, [C.c_void_p, P(C.c_int8), P(C.c_uint64)]),
+    "lc_setfull_stream_ids": (C.c_int64, [C.c_void_p, C.c_int64, P(C.c_int64), C.c_int64]),
+    "lc_setfull_stream_results": (C.c_int, [C.c_void_p, P(LcSetFullResult)]),
+    "lc_setfull_stream_keys": (C.c_int64, [C.c_void_p, P(C.c_int64)]),
+    "lc_setfull_stream_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_setfull_stream_multiplicity": (C.c_int, [C.c_void_p, C.c_int64, P(C.c_uint32), C.c_int64]),
+    "lc_setfull_stream_last_chunk": (C.c_int, [C.c_void_p, P(LcSetFullStreamChunk)]),
+    "lc_setfull_stream_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_setfull_stream_close": (None, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -345,7 +379,7 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SETFULL_STREAM_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -359,6 +359,15 @@ class SetFullChecker:
         from . import checker as ck
         return ck.device_for(self.device)
 
+    def stream(self, dev=None):
+        """A streaming check under this checker's options
+        (lincheck.setfull_stream.SetFullStream): rows are appended while the
+        test runs, and after every append the results are those of check() on
+        everything appended so far."""
+        from .setfull_stream import SetFullStream
+        return SetFullStream(dev if dev is not None else self.dev(),
+                             {"linearizable?": self.linearizable, "max-matrix-bytes": self.max_matrix_bytes})
+
     def _check(self, history):
         hist = history if isinstance(history, SetFullHistory) else SetFullHistory.from_ops(history)
         packed = PackedSetFull(hist)
