@@ -43,7 +43,8 @@ def batch():
 def _dev(segs, ck, **kw):
     if ck is not None:
         kw["spec_ck"] = ck
-    return Device(0, path_flags=N.LC_PATH_SPLIT_OFF, spec_segs=segs, **kw)
+    kw.setdefault("path_flags", N.LC_PATH_SPLIT_OFF)
+    return Device(0, spec_segs=segs, **kw)
 
 
 def test_batch_holds_what_it_should(batch):
@@ -76,6 +77,12 @@ def test_verdicts(batch, segs, ck):
     for f in ("valid", "cause", "fail_event"):
         np.testing.assert_array_equal(getattr(r, f), batch.orc[f], err_msg=f"oracle: {f}")
         np.testing.assert_array_equal(getattr(r, f), getattr(batch.plain, f), err_msg=f"unsegmented: {f}")
+    if (segs, ck) == (4, None):
+        # no staging: every key's event words read from HBM, every key validated by the validation blocks
+        r = _dev(segs, ck, path_flags=N.LC_PATH_SPLIT_OFF | N.LC_PATH_SPEC_NOSTAGE).check(batch.pk, verdicts_only=True)
+        assert r.stats["t0_path"] == "k_spec"
+        for f in ("valid", "cause", "fail_event"):
+            np.testing.assert_array_equal(getattr(r, f), batch.orc[f], err_msg=f"NOSTAGE, oracle: {f}")
 
 
 @pytest.mark.parametrize("segs,ck", RUNS, ids=[f"segs{s}-{'ck0' if c else 'default'}" for s, c in RUNS])
