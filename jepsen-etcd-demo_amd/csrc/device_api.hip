@@ -25,6 +25,7 @@
 #include <thread>
 
 #include "device_ctx.hpp"
+#include "counter_plan.hpp"
 
 using namespace lcx;
 
@@ -1768,6 +1769,156 @@ extern "C" int lc_setfull_last_timing(lc_ctx *c, double *out8) {
     if (!c || !out8) return lc::fail(LC_E_INVALID, "lc_setfull_last_timing: null argument");
     std::lock_guard<std::mutex> g(c->mu);
     return lcf::setfull_last_timing(c->dev[0]->setfulldev, out8);
+}
+
+// ---- checker/counter (include/lincheck_counter.h; kernels: device_counter.hip) ----
+
+namespace {
+
+// Sections of a block, each 16-byte aligned.
+struct CtLayout {
+    size_t at = 0;
+    size_t take(size_t bytes) {
+        const size_t o = at;
+        at += (bytes + 15) & ~(size_t)15;
+        return o;
+    }
+};
+
+int counter_check(CounterDev &D, hipStream_t stream, const lc_counter_batch *b, uint32_t tile, lc_counter_result *r) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    const int64_t K = b->n_keys;
+    const size_t nk = (size_t)K;
+    const uint64_t E = b->ev_off[K], R = b->read_off[K];
+    const uint64_t te = lcc::ct_tiles(E, tile), tr = lcc::ct_tiles(R, tile), tmax = std::max(te, tr);
+    if (tmax > lcc::CT_MAX_TILES) return lc::fail(LC_E_INVALID, "lc_counter_check: more than 2^31 tiles");
+    for (hipEvent_t &e : D.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    std::vector<uint32_t> first_ev, first_rd;
+    try {
+        if (E) first_ev = lcc::ct_first_key(b->ev_off, K, E, tile);
+        if (R) first_rd = lcc::ct_first_key(b->read_off, K, R, tile);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_counter_check: out of memory");
+    }
+    // one metadata block, one copy
+    CtLayout L;
+    const size_t o_ev_off = L.take((nk + 1) * 8), o_rd_off = L.take((nk + 1) * 8);
+    const size_t o_first_ev = L.take(first_ev.size() * 4), o_first_rd = L.take(first_rd.size() * 4);
+    HIPCHK(grow_pinned(D.hmeta, D.hmeta_cap, L.at));
+    HIPCHK(grow_pinned(D.hout, D.hout_cap, (size_t)2));
+    std::memcpy(D.hmeta + o_ev_off, b->ev_off, (nk + 1) * 8);
+    std::memcpy(D.hmeta + o_rd_off, b->read_off, (nk + 1) * 8);
+    if (E) std::memcpy(D.hmeta + o_first_ev, first_ev.data(), first_ev.size() * 4);
+    if (R) std::memcpy(D.hmeta + o_first_rd, first_rd.data(), first_rd.size() * 4);
+    CtLayout T;  // the tile records and carries, shared by the two scans
+    const size_t o_sa = T.take(tmax * 8), o_sb = T.take(tmax * 8), o_ca = T.take(tmax * 8), o_cb = T.take(tmax * 8);
+    const size_t o_hd = T.take(tmax);
+    char *meta, *tiles;
+    uint8_t *kind;
+    int64_t *val, *rval, *lower, *upper;
+    unsigned long long *err_off, *err_idx, *out;
+    HIPCHK(grow(D.mem[CounterDev::META], meta, L.at));
+    HIPCHK(grow(D.mem[CounterDev::KIND], kind, (size_t)E));
+    HIPCHK(grow(D.mem[CounterDev::VAL], val, (size_t)E));
+    HIPCHK(grow(D.mem[CounterDev::RVAL], rval, (size_t)R));
+    HIPCHK(grow(D.mem[CounterDev::LOWER], lower, (size_t)R));
+    HIPCHK(grow(D.mem[CounterDev::UPPER], upper, (size_t)R));
+    HIPCHK(grow(D.mem[CounterDev::TILES], tiles, T.at));
+    HIPCHK(grow(D.mem[CounterDev::ERR_OFF], err_off, nk + 1));
+    HIPCHK(grow(D.mem[CounterDev::ERR_IDX], err_idx, (size_t)std::min<uint64_t>(r->err_cap, R)));
+    HIPCHK(grow(D.mem[CounterDev::OUT], out, (size_t)2));
+    const uint64_t cap = std::min<uint64_t>(r->err_cap, R);  // (no more reads than R can be flagged)
+
+    HIPCHK(hipEventRecord(D.ev[0], stream));
+    HIPCHK(hipMemcpyAsync(meta, D.hmeta, L.at, hipMemcpyHostToDevice, stream));
+    if (E) {
+        HIPCHK(hipMemcpyAsync(kind, b->ev_kind, E, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(val, b->ev_val, E * 8, hipMemcpyHostToDevice, stream));
+    }
+    if (R) HIPCHK(hipMemcpyAsync(rval, b->read_val, R * 8, hipMemcpyHostToDevice, stream));
+    HIPCHK(hipEventRecord(D.ev[1], stream));
+    HIPCHK(hipMemsetAsync(out, 0, 16, stream));
+    HIPCHK(hipMemsetAsync(err_off, 0, (nk + 1) * 8, stream));
+    if (R) {
+        HIPCHK(hipMemsetAsync(lower, 0, R * 8, stream));
+        HIPCHK(hipMemsetAsync(upper, 0, R * 8, stream));
+    }
+    lcc::CtTiles ct{(unsigned long long *)(tiles + o_sa), (unsigned long long *)(tiles + o_sb),
+                    (unsigned long long *)(tiles + o_ca), (unsigned long long *)(tiles + o_cb), (uint8_t *)(tiles + o_hd)};
+    if (E) {
+        lcc::CtEvents a{};
+        a.s = lcc::CtSeries{(const uint64_t *)(meta + o_ev_off), (const uint32_t *)(meta + o_first_ev), K, E, te};
+        a.t = ct;
+        a.kind = kind; a.val = val; a.lower = lower; a.upper = upper; a.R = R;
+        a.err = (uint32_t *)(out + 1);
+        HIPCHK(lcc::counter_launch_events(stream, tile, a));
+    }
+    if (R) {
+        lcc::CtJudge a{};
+        a.s = lcc::CtSeries{(const uint64_t *)(meta + o_rd_off), (const uint32_t *)(meta + o_first_rd), K, R, tr};
+        a.t = ct;
+        a.val = rval; a.lower = lower; a.upper = upper;
+        a.err_off = err_off; a.err_idx = err_idx; a.err_cap = cap; a.n_err = out;
+        HIPCHK(lcc::counter_launch_judge(stream, tile, a));
+    }
+    HIPCHK(hipEventRecord(D.ev[2], stream));
+    HIPCHK(hipMemcpyAsync(D.hout, out, 16, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(r->err_off, err_off, (nk + 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (R) {
+        HIPCHK(hipMemcpyAsync(r->lower, lower, R * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(r->upper, upper, R * 8, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipStreamSynchronize(stream));
+    if ((uint32_t)D.hout[1]) return lc::fail(LC_E_INVALID, "lc_counter_check: a bad event kind, or a read event that names no read of the batch");
+    const uint64_t n_err = D.hout[0];
+    r->n_err = n_err;
+    for (int64_t k = 0; k < K; ++k) {
+        r->n_errors[k] = r->err_off[k + 1] - r->err_off[k];
+        r->valid[k] = b->status && b->status[k] != LC_COUNTER_KEY_OK ? LC_UNKNOWN : r->n_errors[k] ? LC_INVALID : LC_VALID;
+    }
+    if (n_err && n_err <= r->err_cap) HIPCHK(hipMemcpyAsync(r->err_idx, err_idx, n_err * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipEventRecord(D.ev[3], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    float f = 0;
+    for (int i = 0; i < 3; ++i) {
+        HIPCHK(hipEventElapsedTime(&f, D.ev[i], D.ev[i + 1]));
+        D.ms[i] = f;
+    }
+    D.ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    if (n_err > r->err_cap)
+        return lc::fail(LC_E_NOMEM, "lc_counter_check: err_cap %llu, %llu needed", (unsigned long long)r->err_cap,
+                        (unsigned long long)n_err);
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_counter_check(lc_ctx *c, const lc_counter_batch *b, const lc_counter_opts *o, lc_counter_result *r) {
+    if (!c || !b || !o || !r) return lc::fail(LC_E_INVALID, "lc_counter_check: null argument");
+    lc::Range range("lc_counter_check");
+    LCCHK(lcc::counter_validate(b, "lc_counter_check"));
+    if (o->flags) return lc::fail(LC_E_INVALID, "lc_counter_check: unknown flags 0x%x", o->flags);
+    const uint32_t tile = lcc::ct_tile_of(o->tile);
+    if (!tile) return lc::fail(LC_E_INVALID, "lc_counter_check: tile %u (256 or 2048)", o->tile);
+    r->n_err = 0;
+    if (b->n_keys == 0) return LC_OK;
+    const uint64_t R = b->read_off[b->n_keys];
+    if (!r->valid || !r->n_errors || !r->err_off || (R && (!r->lower || !r->upper)) || (r->err_cap && !r->err_idx))
+        return lc::fail(LC_E_INVALID, "lc_counter_check: null result array");
+    CtxCall x(c);
+    LCCHK(x.enter());
+    if (!x.d->counterdev) x.d->counterdev = new (std::nothrow) CounterDev();
+    if (!x.d->counterdev) return lc::fail(LC_E_NOMEM, "lc_counter_check: out of memory");
+    return counter_check(*x.d->counterdev, x.d->stream, b, tile, r);
+}
+
+extern "C" int lc_counter_last_timing(lc_ctx *c, double *out4) {
+    if (!c || !out4) return lc::fail(LC_E_INVALID, "lc_counter_last_timing: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    const CounterDev *d = c->dev[0]->counterdev;
+    for (int i = 0; i < 4; ++i) out4[i] = d ? d->ms[i] : 0.0;
+    return LC_OK;
 }
 
 // ---- checker/perf (etcdemo.clj:165-167; device_perf.hip) ----------------------

@@ -15,6 +15,7 @@
 #include "device_perf.hpp"
 #include "device_set.hpp"
 #include "device_setfull.hpp"
+#include "device_counter.hpp"
 #include "step_plan.hpp"
 #include "lane_plan.hpp"
 
@@ -140,6 +141,30 @@ hipError_t grow(DevBatch::Mem &m, T *&p, size_t n) {
     p = (T *)m.p;
     return hipSuccess;
 }
+
+// lc_counter_check's state on a device (device_api.hip; the kernels are
+// device_counter.hip's): cached device arrays, pinned staging and timing
+// events, grown on demand and kept from one call to the next.
+struct CounterDev {
+    // meta: both offset arrays and both first-key arrays (one copy); tiles: the
+    // tile records and carries; out: the error count and the error word
+    enum { META, KIND, VAL, RVAL, LOWER, UPPER, TILES, ERR_OFF, ERR_IDX, OUT, N_MEM };
+    DevBatch::Mem mem[N_MEM];
+    char *hmeta = nullptr;   // pinned staging of meta
+    size_t hmeta_cap = 0;
+    unsigned long long *hout = nullptr;  // pinned landing of out (2 words)
+    size_t hout_cap = 0;
+    hipEvent_t ev[4] = {};
+    double ms[4] = {0, 0, 0, 0};
+    ~CounterDev() {
+        for (DevBatch::Mem &m : mem)
+            if (m.p) (void)hipFree(m.p);
+        if (hmeta) (void)hipHostFree(hmeta);
+        if (hout) (void)hipHostFree(hout);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
 
 // What a search step reaches through stream order, one copy per search
 // lane: consecutive enqueued register-tier steps of lc_check_node_async
@@ -286,6 +311,7 @@ struct Dev {
     lcs::SetDev *setdev = nullptr;  // lc_set_check's cached arrays (device_set.hip), made on first use
     lcp::PerfDev *perfdev = nullptr;  // lc_perf_check's (device_perf.hip), likewise
     lcf::SetFullDev *setfulldev = nullptr;  // lc_setfull_check's (device_setfull.hip), likewise
+    CounterDev *counterdev = nullptr;  // lc_counter_check's (device_api.hip), likewise
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
@@ -293,6 +319,7 @@ struct Dev {
         lcs::set_dev_free(setdev);
         lcp::perf_dev_free(perfdev);
         lcf::setfull_dev_free(setfulldev);
+        delete counterdev;
         dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
         dfree(peak); dfree(final_cfg); dfree(n_final);

@@ -1228,3 +1228,148 @@ extern "C" int lc_setfull_hist_view(const lc_setfull_hist *h, lc_setfull_history
 }
 
 extern "C" void lc_setfull_hist_free(lc_setfull_hist *h) { delete h; }
+
+// ---- history.edn for checker/counter (include/lincheck_counter.h) ----------------
+// A fourth op handler over the same reader: :type, :f (:add / :read, anything
+// else LC_CF_OTHER), :process, :index and the :value, which is an integer or
+// nil, or either inside an independent tuple [k v] -- a two-element vector
+// whose first element is an integer.  Any other value reads as LC_NIL.
+// Single-threaded.
+
+#include "../../include/lincheck_counter.h"
+
+struct lc_counter_hist {
+    std::vector<uint8_t> type, f;
+    std::vector<int64_t> process, key, value, index;
+};
+
+namespace {
+
+bool read_counter_op(Parser &ps, lc_counter_hist &h) {
+    ++ps.p;  // at '{'
+    uint8_t type = 255, f = LC_CF_OTHER;
+    int64_t process = LC_NO_PROCESS, index = -1;
+    Top value;
+    value.kind = K_NIL;
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated op map");
+        if (*ps.p == '}') { ++ps.p; break; }
+        std::string_view k;
+        bool is_kw = false;
+        if (!ps.keyword(k, is_kw)) return false;
+        if (!is_kw) {
+            if (!ps.skip()) return false;
+            continue;
+        }
+        const Field fld = field_of(k);
+        if (fld == FLD_TYPE || fld == FLD_F) {
+            std::string_view v;
+            bool vk = false;
+            if (!ps.keyword(v, vk)) return false;
+            if (fld == FLD_TYPE) {
+                if (!vk) return ps.fail(":type is not a keyword");
+                switch (pack8(v)) {
+                    case P8("invoke"): type = LC_INVOKE; break;
+                    case P8("ok"): type = LC_OK_T; break;
+                    case P8("fail"): type = LC_FAIL; break;
+                    case P8("info"): type = LC_INFO; break;
+                    default: return ps.fail("unknown :type :" + std::string(v));
+                }
+            } else {
+                f = !vk ? LC_CF_OTHER : pack8(v) == P8("add") ? LC_CF_ADD : pack8(v) == P8("read") ? LC_CF_READ : LC_CF_OTHER;
+            }
+        } else if (fld == FLD_PROCESS || fld == FLD_INDEX) {
+            Leaf v;
+            if (!ps.shaped(v)) return false;
+            if (fld == FLD_PROCESS) process = v.kind == K_INT ? v.i : LC_NO_PROCESS;
+            else index = v.kind == K_INT ? v.i : -1;
+        } else if (fld == FLD_VALUE) {
+            if (!ps.shaped(value)) return false;
+        } else {
+            if (!ps.skip()) return false;
+        }
+    }
+    if (type == 255) return ps.fail("op map without :type");
+    int64_t key = LC_NO_KEY, v = LC_NIL;
+    if (f != LC_CF_OTHER) {
+        if (value.kind == K_VEC && value.n == 2 && value.e[0].kind == K_INT) {
+            key = value.e[0].i;
+            if (value.e[1].kind == K_INT) v = value.e[1].i;
+        } else if (value.kind == K_INT) {
+            v = value.i;
+        }
+    }
+    h.type.push_back(type); h.f.push_back(f); h.process.push_back(process); h.key.push_back(key);
+    h.value.push_back(v); h.index.push_back(index);
+    return true;
+}
+
+int parse_counter(const char *text, int64_t len, lc_counter_hist **out) {
+    Parser ps{text, text + len, text};
+    auto h = std::make_unique<lc_counter_hist>();
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) break;
+        if (*ps.p == '{') {
+            if (!read_counter_op(ps, *h)) break;
+        } else if (*ps.p == '[') {  // a vector of op maps
+            ++ps.p;
+            bool closed = false;
+            for (;;) {
+                ps.ws();
+                if (ps.p >= ps.end) { ps.fail("unterminated history vector"); break; }
+                if (*ps.p == ']') { ++ps.p; closed = true; break; }
+                if (*ps.p != '{') { ps.fail("expected an op map"); break; }
+                if (!read_counter_op(ps, *h)) break;
+            }
+            if (!closed) break;
+        } else {
+            ps.fail("expected an op map");
+            break;
+        }
+    }
+    if (!ps.err.empty())
+        return lc::fail(LC_E_PARSE, "lc_edn_counter: line %lld: %s", (long long)line_of(text, ps.err_off), ps.err.c_str());
+    *out = h.release();
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_edn_parse_counter(const char *text, int64_t len, lc_counter_hist **out) {
+    lc::Range range("lc_edn_parse_counter");
+    if (!text || !out || len < 0) return lc::fail(LC_E_INVALID, "lc_edn_parse_counter: null argument");
+    try {
+        return parse_counter(text, len, out);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_edn_counter: out of memory");
+    }
+}
+
+extern "C" int lc_edn_read_counter(const char *path, lc_counter_hist **out) {
+    if (!path || !out) return lc::fail(LC_E_INVALID, "lc_edn_read_counter: null argument");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return lc::fail(LC_E_IO, "lc_edn_read_counter: cannot open %s", path);
+    std::string s;
+    try {
+        char buf[1 << 16];
+        size_t r;
+        while ((r = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, r);
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return lc::fail(LC_E_NOMEM, "lc_edn_read_counter: out of memory");
+    }
+    std::fclose(f);
+    return lc_edn_parse_counter(s.data(), (int64_t)s.size(), out);
+}
+
+extern "C" int lc_counter_hist_view(const lc_counter_hist *h, lc_counter_history *out) {
+    if (!h || !out) return lc::fail(LC_E_INVALID, "lc_counter_hist_view: null argument");
+    out->n = (int64_t)h->type.size();
+    out->type = h->type.data(); out->f = h->f.data(); out->process = h->process.data(); out->key = h->key.data();
+    out->value = h->value.data(); out->index = h->index.data();
+    return LC_OK;
+}
+
+extern "C" void lc_counter_hist_free(lc_counter_hist *h) { delete h; }

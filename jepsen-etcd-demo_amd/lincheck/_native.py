@@ -363,6 +363,48 @@ SETFULL_STREAM_SIGNATURES = {
     "lc_setfull_stream_close": (None, [C.c_void_p]),
 }
 
+# ---- checker/counter (include/lincheck_counter.h; ABI 13, additive) ----------------
+# A header and a table of their own, as the streaming set-full's.
+LC_CF_ADD, LC_CF_READ, LC_CF_OTHER = 0, 1, 2
+LC_CE_UP, LC_CE_LOW, LC_CE_RINV, LC_CE_ROK = 0, 1, 2, 3
+LC_COUNTER_KEY_OK, LC_COUNTER_KEY_ERROR = 0, 1
+
+
+class LcCounterHistory(C.Structure):
+    _fields_ = [("n", C.c_int64), ("type", P(C.c_uint8)), ("f", P(C.c_uint8)), ("process", P(C.c_int64)),
+                ("key", P(C.c_int64)), ("value", P(C.c_int64)), ("index", P(C.c_int64))]
+
+
+class LcCounterBatch(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("ev_off", P(C.c_uint64)), ("ev_kind", P(C.c_uint8)), ("ev_val", P(C.c_int64)),
+                ("read_off", P(C.c_uint64)), ("read_val", P(C.c_int64)), ("status", P(C.c_uint8))]
+
+
+class LcCounterOpts(C.Structure):
+    _fields_ = [("tile", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LcCounterResult(C.Structure):
+    _fields_ = [("valid", P(C.c_int8)), ("n_errors", P(C.c_uint64)), ("lower", P(C.c_int64)), ("upper", P(C.c_int64)),
+                ("err_off", P(C.c_uint64)), ("err_idx", P(C.c_uint64)), ("err_cap", C.c_uint64), ("n_err", C.c_uint64)]
+
+
+COUNTER_SIGNATURES = {
+    "lc_counter_pack": (C.c_int, [P(LcCounterHistory), P(C.c_void_p)]),
+    "lc_counter_packed_free": (None, [C.c_void_p]),
+    "lc_counter_packed_view": (C.c_int, [C.c_void_p, P(LcCounterBatch)]),
+    "lc_counter_packed_keys": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_counter_packed_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_counter_check": (C.c_int, [C.c_void_p, P(LcCounterBatch), P(LcCounterOpts), P(LcCounterResult)]),
+    "lc_counter_check_host": (C.c_int, [P(LcCounterBatch), P(LcCounterResult)]),
+    "lc_counter_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_counter_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_edn_read_counter": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+    "lc_edn_parse_counter": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
+    "lc_counter_hist_view": (C.c_int, [C.c_void_p, P(LcCounterHistory)]),
+    "lc_counter_hist_free": (None, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -379,7 +421,7 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SETFULL_STREAM_SIGNATURES.items()):
+        for name, (res, args) in list(SIGNATURES.items()) + list(SETFULL_STREAM_SIGNATURES.items()) + list(COUNTER_SIGNATURES.items()):
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

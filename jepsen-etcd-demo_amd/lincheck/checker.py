@@ -17,6 +17,10 @@
     perf()
         jepsen.checker/perf (etcdemo.clj:166): always valid; the latency and
         rate series computed on the device: lincheck.perf.
+    counter()
+        jepsen.checker/counter: every :ok read's value against the sum of the
+        acknowledged adds at its invocation and of the attempted adds at its
+        completion, by a prefix scan on the device: lincheck.counter.
 
 Under independent.checker the linearizable check is batched: every key goes
 to the device in one call (Batch below).  Device failures raise; check_safe
@@ -776,14 +780,24 @@ def perf(opts: Optional[Dict] = None):
     return PerfChecker(opts)
 
 
+def counter(opts: Optional[Dict] = None):
+    """jepsen.checker/counter: the bounds of every read of a counter, by a
+    prefix scan on the device (lincheck.counter).  opts: {"tile": 256 | 2048,
+    "host": bool -- lc_counter_check_host's plain fold, no device}."""
+    from .counter import CounterChecker
+    return CounterChecker(opts)
+
+
 def batched_set(inner):
-    """The SetChecker (or SetFullChecker) inside `inner` if independent.checker can batch it."""
+    """The SetChecker (or SetFullChecker, or CounterChecker) inside `inner` if independent.checker can batch it."""
+    from .counter import CounterChecker
     from .setcheck import SetChecker
     from .setfull import SetFullChecker
-    if isinstance(inner, (SetChecker, SetFullChecker)):
+    kinds = (SetChecker, SetFullChecker, CounterChecker)
+    if isinstance(inner, kinds):
         return inner
     if isinstance(inner, Compose):
-        sets = [c for c in inner.checkers.values() if isinstance(c, (SetChecker, SetFullChecker))]
+        sets = [c for c in inner.checkers.values() if isinstance(c, kinds)]
         if len(sets) == 1 and not any(isinstance(c, Linearizable) for c in inner.checkers.values()):
             return sets[0]
     return None
