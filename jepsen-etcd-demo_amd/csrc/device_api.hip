@@ -26,6 +26,7 @@
 
 #include "device_ctx.hpp"
 #include "counter_plan.hpp"
+#include "queue_plan.hpp"
 
 using namespace lcx;
 
@@ -1917,6 +1918,139 @@ extern "C" int lc_counter_last_timing(lc_ctx *c, double *out4) {
     if (!c || !out4) return lc::fail(LC_E_INVALID, "lc_counter_last_timing: null argument");
     std::lock_guard<std::mutex> g(c->mu);
     const CounterDev *d = c->dev[0]->counterdev;
+    for (int i = 0; i < 4; ++i) out4[i] = d ? d->ms[i] : 0.0;
+    return LC_OK;
+}
+
+// ---- checker/total-queue and /unique-ids (include/lincheck_queue.h; kernels: device_queue.hip) ----
+
+namespace {
+
+int queue_check(QueueDev &D, hipStream_t stream, const lc_queue_batch *b, uint64_t slots, lc_queue_result *r) {
+    const auto wall0 = std::chrono::steady_clock::now();
+    const size_t nk = (size_t)b->n_keys, n = (size_t)b->n_rows;
+    for (hipEvent_t &e : D.ev)
+        if (!e) HIPCHK(hipEventCreate(&e));
+    // the per-key words as one block: counts, lo, hi
+    const size_t o_lo = nk * LC_QN_COUNTS * 8, o_hi = o_lo + nk * 8, keyst_bytes = o_hi + nk * 8;
+    const uint64_t cap = std::min<uint64_t>(r->ent_cap, 2 * (uint64_t)n);  // (a distinct value makes at most two entries)
+    HIPCHK(grow_pinned(D.hkeyst, D.hkeyst_cap, keyst_bytes));
+    HIPCHK(grow_pinned(D.hout, D.hout_cap, (size_t)lcq::QO_WORDS));
+    lcq::QueueArgs a{};
+    uint32_t *row_key;
+    uint8_t *row_kind, *status;
+    int64_t *row_val;
+    char *keyst;
+    HIPCHK(grow(D.mem[QueueDev::ROW_KEY], row_key, n));
+    HIPCHK(grow(D.mem[QueueDev::ROW_KIND], row_kind, n));
+    HIPCHK(grow(D.mem[QueueDev::ROW_VAL], row_val, n));
+    HIPCHK(grow(D.mem[QueueDev::STATUS], status, nk));
+    HIPCHK(grow(D.mem[QueueDev::TABLE], a.table, (size_t)slots));
+    HIPCHK(grow(D.mem[QueueDev::KEYST], keyst, keyst_bytes));
+    HIPCHK(grow(D.mem[QueueDev::ENT_KEY], a.ent_key, (size_t)cap));
+    HIPCHK(grow(D.mem[QueueDev::ENT_CLASS], a.ent_class, (size_t)cap));
+    HIPCHK(grow(D.mem[QueueDev::ENT_VAL], a.ent_val, (size_t)cap));
+    HIPCHK(grow(D.mem[QueueDev::ENT_MULT], a.ent_mult, (size_t)cap));
+    HIPCHK(grow(D.mem[QueueDev::OUT], a.out, (size_t)lcq::QO_WORDS));
+    a.row_key = row_key; a.row_kind = row_kind; a.row_val = row_val; a.status = status;
+    a.n_rows = n; a.K = (uint32_t)nk; a.mode = b->mode; a.slots = (uint32_t)slots;
+    a.counts = (unsigned long long *)keyst;
+    a.lo = (long long *)(keyst + o_lo);
+    a.hi = (long long *)(keyst + o_hi);
+    a.ent_cap = cap;
+    // status is staged in the landing of the per-key words, which the stream fills only after this copy
+    if (b->status) std::memcpy(D.hkeyst, b->status, nk);
+    else std::memset(D.hkeyst, LC_QUEUE_KEY_OK, nk);
+
+    HIPCHK(hipEventRecord(D.ev[0], stream));
+    HIPCHK(hipMemcpyAsync(status, D.hkeyst, nk, hipMemcpyHostToDevice, stream));
+    if (n) {
+        HIPCHK(hipMemcpyAsync(row_key, b->row_key, n * 4, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(row_kind, b->row_kind, n, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(row_val, b->row_val, n * 8, hipMemcpyHostToDevice, stream));
+    }
+    HIPCHK(hipEventRecord(D.ev[1], stream));
+    HIPCHK(lcq::queue_launch(stream, a));
+    HIPCHK(hipEventRecord(D.ev[2], stream));
+    HIPCHK(hipMemcpyAsync(D.hout, a.out, lcq::QO_WORDS * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(D.hkeyst, keyst, keyst_bytes, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (D.hout[lcq::QO_ERR] & lcq::QE_BAD_ROW)
+        return lc::fail(LC_E_INVALID, "lc_queue_check: a row_key that is not below n_keys, or a row_kind the mode has not");
+    if (D.hout[lcq::QO_ERR])
+        return lc::fail(LC_E_INVALID, "lc_queue_check: a row found no slot in a table of %llu", (unsigned long long)slots);
+    std::memcpy(r->counts, D.hkeyst, o_lo);
+    lcq::queue_finish(b, r);
+    for (size_t k = 0; k < nk; ++k)
+        if (r->has_range[k]) {
+            std::memcpy(&r->lo[k], D.hkeyst + o_lo + k * 8, 8);
+            std::memcpy(&r->hi[k], D.hkeyst + o_hi + k * 8, 8);
+        }
+    const uint64_t n_ent = D.hout[lcq::QO_N_ENT];
+    r->n_ent = n_ent;
+    const bool fits = n_ent <= r->ent_cap;
+    size_t o_cls = 0, o_val = 0, o_mult = 0;
+    if (n_ent && fits) {
+        const size_t ne = (size_t)n_ent;  // (n_ent <= 2 n: ne <= cap)
+        o_val = (ne * 4 + 15) & ~(size_t)15; o_mult = o_val + ne * 8; o_cls = o_mult + ne * 8;
+        HIPCHK(grow_pinned(D.hent, D.hent_cap, o_cls + ne));
+        HIPCHK(hipMemcpyAsync(D.hent, a.ent_key, ne * 4, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(D.hent + o_val, a.ent_val, ne * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(D.hent + o_mult, a.ent_mult, ne * 8, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipMemcpyAsync(D.hent + o_cls, a.ent_class, ne, hipMemcpyDeviceToHost, stream));
+    }
+    HIPCHK(hipEventRecord(D.ev[3], stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    if (n_ent && fits) {
+        try {
+            // the device's order is unspecified: the call returns the entries sorted
+            lcq::queue_sort_entries(r, n_ent, (const uint32_t *)D.hent, (const uint8_t *)(D.hent + o_cls),
+                                    (const int64_t *)(D.hent + o_val), (const unsigned long long *)(D.hent + o_mult));
+        } catch (const std::bad_alloc &) {
+            return lc::fail(LC_E_NOMEM, "lc_queue_check: out of memory");
+        }
+    }
+    float f = 0;
+    for (int i = 0; i < 3; ++i) {
+        HIPCHK(hipEventElapsedTime(&f, D.ev[i], D.ev[i + 1]));
+        D.ms[i] = f;
+    }
+    D.ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
+    if (!fits)
+        return lc::fail(LC_E_NOMEM, "lc_queue_check: ent_cap %llu, %llu needed", (unsigned long long)r->ent_cap,
+                        (unsigned long long)n_ent);
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_queue_check(lc_ctx *c, const lc_queue_batch *b, const lc_queue_opts *o, lc_queue_result *r) {
+    if (!c || !b || !o || !r) return lc::fail(LC_E_INVALID, "lc_queue_check: null argument");
+    lc::Range range("lc_queue_check");
+    LCCHK(lcq::queue_validate(b, r, "lc_queue_check"));
+    if (o->flags) return lc::fail(LC_E_INVALID, "lc_queue_check: unknown flags 0x%x", o->flags);
+    const uint64_t slots = lcq::qp_slots_of(o->slots, (uint64_t)b->n_rows);
+    if (slots == lcq::QP_BAD_SLOTS)
+        return lc::fail(LC_E_INVALID, "lc_queue_check: slots %u (a power of two, at least the %lld rows)", o->slots, (long long)b->n_rows);
+    if (!lcq::qp_fits(slots))
+        return lc::fail(LC_E_NOMEM, "lc_queue_check: a table of %llu slots needs %llu bytes, the cap is %llu", (unsigned long long)slots,
+                        (unsigned long long)lcq::qp_bytes(slots), (unsigned long long)lcq::QP_MAX_BYTES);
+    r->n_ent = 0;
+    if (b->n_keys == 0) {
+        if (b->n_rows) return lc::fail(LC_E_INVALID, "lc_queue_check: rows without a key");
+        return LC_OK;
+    }
+    CtxCall x(c);
+    LCCHK(x.enter());
+    if (!x.d->queuedev) x.d->queuedev = new (std::nothrow) QueueDev();
+    if (!x.d->queuedev) return lc::fail(LC_E_NOMEM, "lc_queue_check: out of memory");
+    return queue_check(*x.d->queuedev, x.d->stream, b, slots, r);
+}
+
+extern "C" int lc_queue_last_timing(lc_ctx *c, double *out4) {
+    if (!c || !out4) return lc::fail(LC_E_INVALID, "lc_queue_last_timing: null argument");
+    std::lock_guard<std::mutex> g(c->mu);
+    const QueueDev *d = c->dev[0]->queuedev;
     for (int i = 0; i < 4; ++i) out4[i] = d ? d->ms[i] : 0.0;
     return LC_OK;
 }

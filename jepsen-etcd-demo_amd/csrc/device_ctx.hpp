@@ -16,6 +16,7 @@
 #include "device_set.hpp"
 #include "device_setfull.hpp"
 #include "device_counter.hpp"
+#include "device_queue.hpp"
 #include "step_plan.hpp"
 #include "lane_plan.hpp"
 
@@ -160,6 +161,33 @@ struct CounterDev {
         for (DevBatch::Mem &m : mem)
             if (m.p) (void)hipFree(m.p);
         if (hmeta) (void)hipHostFree(hmeta);
+        if (hout) (void)hipHostFree(hout);
+        for (hipEvent_t e : ev)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+// lc_queue_check's state on a device (device_api.hip; the kernels are
+// device_queue.hip's): the hash table, the batch's arrays, the per-key words
+// and the entries, pinned landings and timing events, grown on demand and kept
+// from one call to the next.
+struct QueueDev {
+    // keyst: counts [K][7], lo [K], hi [K] in one block (one copy back); out: the entry cursor and the error word
+    enum { ROW_KEY, ROW_KIND, ROW_VAL, STATUS, TABLE, KEYST, ENT_KEY, ENT_CLASS, ENT_VAL, ENT_MULT, OUT, N_MEM };
+    DevBatch::Mem mem[N_MEM];
+    char *hkeyst = nullptr;  // pinned landing of keyst, and staging of status before it
+    size_t hkeyst_cap = 0;
+    char *hent = nullptr;    // pinned landing of the four entry arrays
+    size_t hent_cap = 0;
+    unsigned long long *hout = nullptr;  // pinned landing of out
+    size_t hout_cap = 0;
+    hipEvent_t ev[4] = {};
+    double ms[4] = {0, 0, 0, 0};
+    ~QueueDev() {
+        for (DevBatch::Mem &m : mem)
+            if (m.p) (void)hipFree(m.p);
+        if (hkeyst) (void)hipHostFree(hkeyst);
+        if (hent) (void)hipHostFree(hent);
         if (hout) (void)hipHostFree(hout);
         for (hipEvent_t e : ev)
             if (e) (void)hipEventDestroy(e);
@@ -312,6 +340,7 @@ struct Dev {
     lcp::PerfDev *perfdev = nullptr;  // lc_perf_check's (device_perf.hip), likewise
     lcf::SetFullDev *setfulldev = nullptr;  // lc_setfull_check's (device_setfull.hip), likewise
     CounterDev *counterdev = nullptr;  // lc_counter_check's (device_api.hip), likewise
+    QueueDev *queuedev = nullptr;  // lc_queue_check's (device_api.hip), likewise
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
@@ -320,6 +349,7 @@ struct Dev {
         lcp::perf_dev_free(perfdev);
         lcf::setfull_dev_free(setfulldev);
         delete counterdev;
+        delete queuedev;
         dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
         dfree(peak); dfree(final_cfg); dfree(n_final);

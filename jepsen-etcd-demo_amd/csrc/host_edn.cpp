@@ -1373,3 +1373,227 @@ extern "C" int lc_counter_hist_view(const lc_counter_hist *h, lc_counter_history
 }
 
 extern "C" void lc_counter_hist_free(lc_counter_hist *h) { delete h; }
+
+// ---- history.edn for checker/total-queue and /unique-ids (include/lincheck_queue.h) ----
+// A fifth op handler over the same reader: :type, :f (:enqueue / :dequeue /
+// :drain / :generate, anything else LC_QF_OTHER) and the :value.  The value's
+// text is skipped where it stands and read again once the op's :f is known: an
+// integer or nil, a drain's vector of them, or either inside an independent
+// tuple [k v].  A value of any other shape ends the read with
+// LC_E_UNSUPPORTED.  Single-threaded.
+
+#include "../../include/lincheck_queue.h"
+
+struct lc_queue_hist {
+    std::vector<uint8_t> type, f;
+    std::vector<int64_t> key, value, drain_val;
+    std::vector<uint64_t> drain_off{0};
+    // one value's elements while it is read: kinds (K_VEC: an integer vector, kept in inner) and integers
+    std::vector<uint8_t> ek;
+    std::vector<int64_t> ei, inner;
+};
+
+namespace {
+
+// The elements of the vector at ps.p ('[' taken) up to its ']': integers and
+// nils into ints; anything else makes `plain` false (and is skipped).
+bool read_int_vector(Parser &ps, std::vector<int64_t> &ints, bool &plain) {
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated collection");
+        if (*ps.p == ']') { ++ps.p; return true; }
+        Leaf e;
+        if (!ps.shaped(e)) return false;
+        if (e.kind == K_INT) ints.push_back(e.i);
+        else if (e.kind == K_NIL) ints.push_back(LC_NIL);
+        else plain = false;
+    }
+}
+
+// The :value at ps.p of an op whose :f is f.  shape_ok comes back false for a
+// value the rules have no reading of.
+bool read_queue_value(Parser &ps, uint8_t f, lc_queue_hist &h, int64_t &key, int64_t &v, bool &shape_ok) {
+    key = LC_NO_KEY;
+    v = LC_NIL;
+    shape_ok = true;
+    if (!ps.prefixes()) return false;
+    const bool drain = f == LC_QF_DRAIN;
+    if (*ps.p != '[') {
+        Leaf s;
+        if (!ps.shaped(s)) return false;
+        if (s.kind == K_INT && !drain) v = s.i;
+        else if (s.kind != K_NIL) shape_ok = false;
+        return true;
+    }
+    ++ps.p;
+    h.ek.clear(); h.ei.clear(); h.inner.clear();
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated collection");
+        if (*ps.p == ']') { ++ps.p; break; }
+        if (!ps.prefixes()) return false;
+        if (*ps.p == '[') {
+            ++ps.p;
+            bool plain = h.ek.size() == 1 && drain;  // only a tuple's second element may be a vector
+            h.inner.clear();
+            if (!read_int_vector(ps, h.inner, plain)) return false;
+            h.ek.push_back(plain ? K_VEC : K_OTHER);
+            h.ei.push_back(0);
+        } else {
+            Leaf e;
+            if (!ps.shaped(e)) return false;
+            h.ek.push_back(e.kind);
+            h.ei.push_back(e.kind == K_INT ? e.i : LC_NIL);
+        }
+    }
+    const size_t n = h.ek.size();
+    if (n == 2 && h.ek[0] == K_INT && (drain ? h.ek[1] == K_NIL || h.ek[1] == K_VEC : h.ek[1] == K_INT || h.ek[1] == K_NIL)) {
+        key = h.ei[0];
+        if (!drain) v = h.ei[1];
+        else if (h.ek[1] == K_VEC) h.drain_val.insert(h.drain_val.end(), h.inner.begin(), h.inner.end());
+        return true;
+    }
+    if (!drain) { shape_ok = false; return true; }
+    for (size_t i = 0; i < n; ++i)
+        if (h.ek[i] != K_INT && h.ek[i] != K_NIL) { shape_ok = false; return true; }
+    h.drain_val.insert(h.drain_val.end(), h.ei.begin(), h.ei.end());
+    return true;
+}
+
+bool read_queue_op(Parser &ps, lc_queue_hist &h, bool &unsupported) {
+    ++ps.p;  // at '{'
+    uint8_t type = 255, f = LC_QF_OTHER;
+    const char *vb = nullptr;
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) return ps.fail("unterminated op map");
+        if (*ps.p == '}') { ++ps.p; break; }
+        std::string_view k;
+        bool is_kw = false;
+        if (!ps.keyword(k, is_kw)) return false;
+        if (!is_kw) {
+            if (!ps.skip()) return false;
+            continue;
+        }
+        const Field fld = field_of(k);
+        if (fld == FLD_TYPE || fld == FLD_F) {
+            std::string_view v;
+            bool vk = false;
+            if (!ps.keyword(v, vk)) return false;
+            if (fld == FLD_TYPE) {
+                if (!vk) return ps.fail(":type is not a keyword");
+                switch (pack8(v)) {
+                    case P8("invoke"): type = LC_INVOKE; break;
+                    case P8("ok"): type = LC_OK_T; break;
+                    case P8("fail"): type = LC_FAIL; break;
+                    case P8("info"): type = LC_INFO; break;
+                    default: return ps.fail("unknown :type :" + std::string(v));
+                }
+            } else if (vk) {
+                switch (pack8(v)) {
+                    case P8("enqueue"): f = LC_QF_ENQUEUE; break;
+                    case P8("dequeue"): f = LC_QF_DEQUEUE; break;
+                    case P8("drain"): f = LC_QF_DRAIN; break;
+                    case P8("generate"): f = LC_QF_GENERATE; break;
+                    default: f = LC_QF_OTHER;
+                }
+            }
+        } else if (fld == FLD_VALUE) {
+            ps.ws();
+            vb = ps.p;
+            if (!ps.skip()) return false;
+        } else {
+            if (!ps.skip()) return false;
+        }
+    }
+    if (type == 255) return ps.fail("op map without :type");
+    int64_t key = LC_NO_KEY, v = LC_NIL;
+    if (f != LC_QF_OTHER && vb) {
+        Parser q{vb, ps.end, ps.base};
+        bool shape_ok = true;
+        if (!read_queue_value(q, f, h, key, v, shape_ok)) {
+            ps.p = q.p;
+            return ps.fail(q.err);
+        }
+        if (!shape_ok) {
+            unsupported = true;
+            ps.p = vb;
+            return ps.fail(f == LC_QF_DRAIN ? "a :drain's value is neither nil nor a vector of integers"
+                                            : "a value that is neither an integer nor nil");
+        }
+    }
+    h.type.push_back(type); h.f.push_back(f); h.key.push_back(key); h.value.push_back(v);
+    h.drain_off.push_back(h.drain_val.size());
+    return true;
+}
+
+int parse_queue(const char *text, int64_t len, lc_queue_hist **out) {
+    Parser ps{text, text + len, text};
+    auto h = std::make_unique<lc_queue_hist>();
+    bool unsupported = false;
+    for (;;) {
+        ps.ws();
+        if (ps.p >= ps.end) break;
+        if (*ps.p == '{') {
+            if (!read_queue_op(ps, *h, unsupported)) break;
+        } else if (*ps.p == '[') {  // a vector of op maps
+            ++ps.p;
+            bool closed = false;
+            for (;;) {
+                ps.ws();
+                if (ps.p >= ps.end) { ps.fail("unterminated history vector"); break; }
+                if (*ps.p == ']') { ++ps.p; closed = true; break; }
+                if (*ps.p != '{') { ps.fail("expected an op map"); break; }
+                if (!read_queue_op(ps, *h, unsupported)) break;
+            }
+            if (!closed) break;
+        } else {
+            ps.fail("expected an op map");
+            break;
+        }
+    }
+    if (!ps.err.empty())
+        return lc::fail(unsupported ? LC_E_UNSUPPORTED : LC_E_PARSE, "lc_edn_queue: line %lld: %s",
+                        (long long)line_of(text, ps.err_off), ps.err.c_str());
+    *out = h.release();
+    return LC_OK;
+}
+
+}  // namespace
+
+extern "C" int lc_edn_parse_queue(const char *text, int64_t len, lc_queue_hist **out) {
+    lc::Range range("lc_edn_parse_queue");
+    if (!text || !out || len < 0) return lc::fail(LC_E_INVALID, "lc_edn_parse_queue: null argument");
+    try {
+        return parse_queue(text, len, out);
+    } catch (const std::bad_alloc &) {
+        return lc::fail(LC_E_NOMEM, "lc_edn_queue: out of memory");
+    }
+}
+
+extern "C" int lc_edn_read_queue(const char *path, lc_queue_hist **out) {
+    if (!path || !out) return lc::fail(LC_E_INVALID, "lc_edn_read_queue: null argument");
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return lc::fail(LC_E_IO, "lc_edn_read_queue: cannot open %s", path);
+    std::string s;
+    try {
+        char buf[1 << 16];
+        size_t r;
+        while ((r = std::fread(buf, 1, sizeof buf, f)) > 0) s.append(buf, r);
+    } catch (const std::bad_alloc &) {
+        std::fclose(f);
+        return lc::fail(LC_E_NOMEM, "lc_edn_read_queue: out of memory");
+    }
+    std::fclose(f);
+    return lc_edn_parse_queue(s.data(), (int64_t)s.size(), out);
+}
+
+extern "C" int lc_queue_hist_view(const lc_queue_hist *h, lc_queue_history *out) {
+    if (!h || !out) return lc::fail(LC_E_INVALID, "lc_queue_hist_view: null argument");
+    out->n = (int64_t)h->type.size();
+    out->type = h->type.data(); out->f = h->f.data(); out->key = h->key.data(); out->value = h->value.data();
+    out->drain_off = h->drain_off.data(); out->drain_val = h->drain_val.data();
+    return LC_OK;
+}
+
+extern "C" void lc_queue_hist_free(lc_queue_hist *h) { delete h; }

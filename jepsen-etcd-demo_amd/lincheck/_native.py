@@ -405,6 +405,53 @@ COUNTER_SIGNATURES = {
     "lc_counter_hist_free": (None, [C.c_void_p]),
 }
 
+# ---- checker/total-queue and /unique-ids (include/lincheck_queue.h; ABI 13, additive) ----
+LC_QF_ENQUEUE, LC_QF_DEQUEUE, LC_QF_DRAIN, LC_QF_GENERATE, LC_QF_OTHER = 0, 1, 2, 3, 4
+LC_QM_TOTAL_QUEUE, LC_QM_UNIQUE_IDS = 0, 1
+LC_QK_ATTEMPT, LC_QK_ACK, LC_QK_DEQUEUE = 0, 1, 2
+LC_QUEUE_KEY_OK, LC_QUEUE_KEY_ERROR = 0, 1
+LC_QN_ATTEMPT, LC_QN_ACKNOWLEDGED, LC_QN_OK, LC_QN_UNEXPECTED, LC_QN_DUPLICATED, LC_QN_LOST, LC_QN_RECOVERED = range(7)
+LC_QN_COUNTS = 7
+LC_QC_LOST, LC_QC_UNEXPECTED, LC_QC_DUPLICATED, LC_QC_RECOVERED = 0, 1, 2, 3
+
+
+class LcQueueHistory(C.Structure):
+    _fields_ = [("n", C.c_int64), ("type", P(C.c_uint8)), ("f", P(C.c_uint8)), ("key", P(C.c_int64)),
+                ("value", P(C.c_int64)), ("drain_off", P(C.c_uint64)), ("drain_val", P(C.c_int64))]
+
+
+class LcQueueBatch(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("n_rows", C.c_int64), ("mode", C.c_uint32), ("reserved", C.c_uint32),
+                ("row_key", P(C.c_uint32)), ("row_kind", P(C.c_uint8)), ("row_val", P(C.c_int64)),
+                ("status", P(C.c_uint8)), ("attempted", P(C.c_uint64))]
+
+
+class LcQueueOpts(C.Structure):
+    _fields_ = [("slots", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LcQueueResult(C.Structure):
+    _fields_ = [("valid", P(C.c_int8)), ("counts", P(C.c_uint64)), ("lo", P(C.c_int64)), ("hi", P(C.c_int64)),
+                ("has_range", P(C.c_uint8)), ("ent_key", P(C.c_uint32)), ("ent_class", P(C.c_uint8)),
+                ("ent_val", P(C.c_int64)), ("ent_mult", P(C.c_uint64)), ("ent_cap", C.c_uint64), ("n_ent", C.c_uint64)]
+
+
+QUEUE_SIGNATURES = {
+    "lc_queue_pack": (C.c_int, [P(LcQueueHistory), C.c_uint32, P(C.c_void_p)]),
+    "lc_queue_packed_free": (None, [C.c_void_p]),
+    "lc_queue_packed_view": (C.c_int, [C.c_void_p, P(LcQueueBatch)]),
+    "lc_queue_packed_keys": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_queue_packed_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_queue_check": (C.c_int, [C.c_void_p, P(LcQueueBatch), P(LcQueueOpts), P(LcQueueResult)]),
+    "lc_queue_check_host": (C.c_int, [P(LcQueueBatch), P(LcQueueResult)]),
+    "lc_queue_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_queue_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_edn_read_queue": (C.c_int, [C.c_char_p, P(C.c_void_p)]),
+    "lc_edn_parse_queue": (C.c_int, [C.c_char_p, C.c_int64, P(C.c_void_p)]),
+    "lc_queue_hist_view": (C.c_int, [C.c_void_p, P(LcQueueHistory)]),
+    "lc_queue_hist_free": (None, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -421,7 +468,8 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SIGNATURES.items()) + list(SETFULL_STREAM_SIGNATURES.items()) + list(COUNTER_SIGNATURES.items()):
+        tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES)
+        for name, (res, args) in [item for t in tables for item in t.items()]:
             fn = getattr(L, name)
             fn.restype = res
             fn.argtypes = args

@@ -21,6 +21,14 @@
         jepsen.checker/counter: every :ok read's value against the sum of the
         acknowledged adds at its invocation and of the attempted adds at its
         completion, by a prefix scan on the device: lincheck.counter.
+    total_queue()
+        jepsen.checker/total-queue: what goes into a queue must come out.  The
+        attempted and acknowledged enqueues and the dequeues are tallied per
+        value in a hash table on the device, and every value comes out ok,
+        lost, unexpected, duplicated or recovered: lincheck.queue.
+    unique_ids()
+        jepsen.checker/unique-ids: no :generate op may return an id twice; the
+        same tally: lincheck.queue.
 
 Under independent.checker the linearizable check is batched: every key goes
 to the device in one call (Batch below).  Device failures raise; check_safe
@@ -788,12 +796,30 @@ def counter(opts: Optional[Dict] = None):
     return CounterChecker(opts)
 
 
+def total_queue(opts: Optional[Dict] = None):
+    """jepsen.checker/total-queue: every value's attempted and acknowledged
+    enqueues against its dequeues, tallied in a hash table on the device
+    (lincheck.queue).  opts: {"slots": a power of two at least the number of
+    values, "host": bool -- lc_queue_check_host's plain fold, no device}."""
+    from .queue import TotalQueueChecker
+    return TotalQueueChecker(opts)
+
+
+def unique_ids(opts: Optional[Dict] = None):
+    """jepsen.checker/unique-ids: the ids acknowledged more than once, by the
+    same tally (lincheck.queue).  opts as total_queue's."""
+    from .queue import UniqueIdsChecker
+    return UniqueIdsChecker(opts)
+
+
 def batched_set(inner):
-    """The SetChecker (or SetFullChecker, or CounterChecker) inside `inner` if independent.checker can batch it."""
+    """The SetChecker (or SetFullChecker, CounterChecker, TotalQueueChecker or UniqueIdsChecker) inside `inner` if
+    independent.checker can batch it."""
     from .counter import CounterChecker
+    from .queue import TotalQueueChecker, UniqueIdsChecker
     from .setcheck import SetChecker
     from .setfull import SetFullChecker
-    kinds = (SetChecker, SetFullChecker, CounterChecker)
+    kinds = (SetChecker, SetFullChecker, CounterChecker, TotalQueueChecker, UniqueIdsChecker)
     if isinstance(inner, kinds):
         return inner
     if isinstance(inner, Compose):
