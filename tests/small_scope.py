@@ -25,9 +25,22 @@ in this order:
               value (0, 1, nil), anything else once with the invocation's
               value; an :info retires the process.
 
-Every key's peak is at most 11 configs, so all of them live in the register
-tier; the set tiers (T1, T2, HBM) are out of these scopes' reach and keep
-their own edge suites.
+Every key's peak is at most 11 configs and at most 4 of its ops are pending at
+once, so as enumerated all of them live in the register tier.  widened() takes
+them out of it without changing a record: it inserts n inert ops into every
+key -- a crashed op whose precondition names INERT, a value no op of a scope
+ever writes (cas-register: {:invoke :cas [7 7]} {:info :cas [7 7]}; register:
+{:invoke :read 7} {:info :read 7}), each on a process of its own.  Such an op
+can never be linearized, so it multiplies no config set, but it stays pending
+for good and holds a window slot: 11 of them put every key past the register
+tier's 10 pending ops (the set tier T1, the stream's resident set tier), 62
+put the live ops past the narrow config's 56 slots (the wide HBM tier, window
+slots 62..65 across the two words of a wide config).  valid, peak and probes
+stay the unwidened key's; the failing event moves by the inert invokes before
+it (Widened.expected_fail_event).  Still out of reach: T2, the narrow HBM tier
+and the layered tier (reached only by outgrowing T1, which no small history
+does), mutex4 (a crashed acquire or release is legal in some state: the model
+has no inert op) and table models.
 
 SCOPES[name].keys / .rows / .valid / .invalid are the counts the rule gives
 and the oracle's split (oracle/brute.py = oracle/linear_ref.c on every key);
@@ -46,6 +59,7 @@ from lincheck import history as H
 from lincheck import model as M
 
 VALUES = (0, 1)
+INERT = 7  # the value widened()'s inert ops name: no op of a scope writes it
 READ_VALUES = (0, 1, None)
 OPS = {
     "cas-register": [("read", None), ("write", 0), ("write", 1)] + [("cas", (a, b)) for a in VALUES for b in VALUES],
@@ -53,6 +67,8 @@ OPS = {
     "mutex": [("acquire", None), ("release", None)],
 }
 PROCS_PER_KEY = 8  # process of key k, enumeration process p: 8 * k + p (a key invokes at most 4 ops)
+INERT_PROC_BASE = 1 << 40  # inert op i of key k: INERT_PROC_BASE + n_inert * k + i (live ones stay below 8 * 177,147)
+PLACES = ("head", "mid", "tail")
 
 
 @dataclass(frozen=True)
@@ -120,6 +136,17 @@ def key_ops(events, key=None) -> list:
     return out
 
 
+def round_robin_of(h: H.History, off) -> H.History:
+    """A key-major history's rows (row offsets per key: off), one row of each
+    key in turn (as stream_helpers.merged_round_robin orders them), :index
+    renumbered."""
+    off = np.asarray(off, np.int64)
+    pos = np.arange(len(h), dtype=np.int64) - np.repeat(off[:-1], np.diff(off))
+    perm = np.lexsort((h.key, pos))
+    return H.History(h.type[perm], h.f[perm], h.process[perm], h.key[perm], h.v0[perm], h.v1[perm],
+                     np.arange(len(perm), dtype=np.int64))
+
+
 class Built:
     """A scope enumerated: .events (the key tuples), .hist (key-major History,
     key = enumeration index), .off (row offsets per key, K + 1)."""
@@ -162,11 +189,7 @@ class Built:
     def round_robin(self) -> H.History:
         """The same rows, one row of each key in turn (as
         stream_helpers.merged_round_robin orders them), :index renumbered."""
-        h = self.hist
-        pos = np.arange(len(h), dtype=np.int64) - np.repeat(self.off[:-1], np.diff(self.off))
-        perm = np.lexsort((h.key, pos))
-        return H.History(h.type[perm], h.f[perm], h.process[perm], h.key[perm], h.v0[perm], h.v1[perm],
-                         np.arange(len(perm), dtype=np.int64))
+        return round_robin_of(self.hist, self.off)
 
     def ops(self, k: int) -> list:
         """Key k's unwrapped sub-history as op maps."""
@@ -181,3 +204,90 @@ class Built:
 @lru_cache(maxsize=None)
 def scope(name: str) -> Built:
     return Built(name)
+
+
+class Widened:
+    """A scope with n_inert inert ops in every key (module docstring): .hist
+    (key-major, :index renumbered), .off (row offsets per key), .at (the row of
+    the unwidened key the inert block stands before), and per reduced event of
+    the unwidened keys -- offsets .ev_off, K + 1 -- .ev_shift: the inert invokes
+    placed before it (0 or n_inert)."""
+
+    def __init__(self, built: Built, n_inert: int, place: str):
+        sc, h, off = built.scope, built.hist, built.off
+        if sc.model == "mutex":
+            raise ValueError("mutex has no inert op: a crashed acquire or release is legal in some state")
+        self.built, self.scope, self.n_inert, self.place = built, sc, n_inert, place
+        K, m = built.n_keys, n_inert
+        n = np.diff(off)
+        self.at = {"head": np.zeros(K, np.int64), "mid": n // 2, "tail": np.maximum(n - 1, 0)}[place]
+        self.off = off + 2 * m * np.arange(K + 1, dtype=np.int64)
+        total = int(self.off[-1])
+        pos = np.arange(len(h), dtype=np.int64) - np.repeat(off[:-1], n)
+        after = pos >= np.repeat(self.at, n)
+        old = np.repeat(self.off[:-1], n) + pos + 2 * m * after                        # where the scope's rows go
+        i = np.tile(np.arange(2 * m, dtype=np.int64), K)
+        k = np.repeat(np.arange(K, dtype=np.int64), 2 * m)
+        new = np.repeat(self.off[:-1] + self.at, 2 * m) + i                            # where the inert rows go
+        cas = sc.model == "cas-register"
+        col = {a: np.empty(total, getattr(h, a).dtype) for a in ("type", "f", "process", "key", "v0", "v1")}
+        for a in col:
+            col[a][old] = getattr(h, a)
+        col["type"][new] = np.where(i % 2 == 0, H.TYPES["invoke"], H.TYPES["info"])
+        col["f"][new] = H.FS["cas" if cas else "read"]
+        col["process"][new] = INERT_PROC_BASE + m * k + i // 2
+        col["key"][new] = k
+        col["v0"][new] = INERT
+        col["v1"][new] = INERT if cas else H.NIL
+        self.hist = H.History(col["type"], col["f"], col["process"], col["key"], col["v0"], col["v1"],
+                              np.arange(total, dtype=np.int64))
+        # The unwidened keys' reduced events: every :ok row, and every :invoke
+        # row but those a :fail answers.  A key's processes alternate :invoke
+        # and completion, so by (process, row) an :invoke's completion, if it
+        # has one, is the next row.
+        order = np.lexsort((np.arange(len(h)), h.process))
+        t, p = h.type[order], h.process[order]
+        failed = np.zeros(len(h), bool)
+        failed[:-1] = (t[:-1] == H.TYPES["invoke"]) & (p[1:] == p[:-1]) & (t[1:] == H.TYPES["fail"])
+        is_event = np.zeros(len(h), bool)
+        is_event[order] = ((t == H.TYPES["invoke"]) & ~failed) | (t == H.TYPES["ok"])
+        self.ev_off = np.concatenate([[0], np.cumsum(is_event)])[off]
+        self.ev_shift = np.where(after[is_event], m, 0).astype(np.int64)
+
+    @property
+    def n_keys(self) -> int:
+        return self.built.n_keys
+
+    def expected_fail_event(self, fail_event) -> np.ndarray:
+        """The widened keys' failing events from the unwidened ones (-1 stays)."""
+        fe = np.asarray(fail_event, np.int64)
+        bad = fe >= 0
+        out = fe.copy()
+        out[bad] += self.ev_shift[self.ev_off[:-1][bad] + fe[bad]]
+        return out
+
+    def slice(self, lo: int, hi: int) -> H.History:
+        a, b = int(self.off[lo]), int(self.off[hi])
+        h = self.hist
+        return H.History(h.type[a:b], h.f[a:b], h.process[a:b], h.key[a:b], h.v0[a:b], h.v1[a:b], h.index[a:b])
+
+    def round_robin(self, lo: int = 0, hi: int = None) -> H.History:
+        """Keys lo .. hi, one row of each key in turn, by Built.round_robin's rule."""
+        hi = self.n_keys if hi is None else hi
+        return round_robin_of(self.slice(lo, hi), self.off[lo:hi + 1] - self.off[lo])
+
+    def ops(self, k: int) -> list:
+        """Key k's unwrapped sub-history as op maps (:index from 0)."""
+        lo, hi = int(self.off[k]), int(self.off[k + 1])
+        out = [self.hist.sub_op(r) for r in range(lo, hi)]
+        for i, o in enumerate(out):
+            o["index"] = i
+        return out
+
+    def describe(self, k: int) -> str:
+        return (f"{self.built.describe(k)} + {self.n_inert} inert ops before row {int(self.at[k])} "
+                f"({self.place})")
+
+
+def widened(built: Built, n_inert: int, place: str) -> Widened:
+    return Widened(built, n_inert, place)

@@ -16,6 +16,40 @@ every batched call asserts the path it ran on.
   (h) test_stream              cas3, one row of each key in turn: plain, exact, set_tier, both
   (i) test_row_order           the one-shot check of that row order
 
+As enumerated every key stays in the register tier (peaks of at most 11
+configs, at most 4 ops pending), so in leg (h) no key migrates: its set_tier
+runs prove only that nothing migrates needlessly.  small_scope.widened takes
+every key of cas2, cas3, cas4p2 and reg4 out of the register tier with inert
+ops -- crashed ops that can never be linearized, 11 or 62 a key, before the
+key's first row (head), its middle row (mid) or its last row (tail) -- and the
+records stay the unwidened key's (tests/test_small_scope.py); the oracle here
+is cref on the widened history.  Each leg asserts the tier that answered:
+
+  (j) test_t1*                 + 11: k_search_lds (T1), every placement; probes, verdicts only, no peaks, node
+                               records, final configs (cas2; cas3 head: the unwidened configs << 11), budgets
+                               1 .. 12 (cas3 mid).  Every key_width is above the register tier's 10 and no key
+                               is handed past T2 (deep_keys 0)
+  (k) test_wide_hbm*           + 62: launch_t3_wide, the live ops in window slots 62 .. 65; probes, final
+                               configs (cas2; cas3 head: the unwidened configs << 62, slot bits in both words),
+                               budgets 1 .. 3.  Every key passes slot 55; deep_keys = keys
+  (l) test_wgl_widened, test_competition_widened
+  (m) test_stream_set_*        + 11, one row of each key in turn: k_stream_migrate, then k_stream_set /
+                               k_stream_set_exact on every key (cas2 in one stream, cas3 mid in streams of
+                               2,048 keys); reports in the append the decided-prefix rule names, key_tier
+                               set / dead, deferred_at, nothing deferred or fallen back, exact: peaks and
+                               final configs against (j)'s one-shot run
+  (n) test_stream_without_the_set_tier   cas2 + 11 mid: dead before the inert block or answered by finish
+
+lc_stats.lds_keys (keys_done in Device.check's stats) counts the keys finished
+in any tier, the HBM tiers included, so it says that every key was answered,
+not where: the tier follows from key_width -- the register tier's kernels
+return K_SPILL above 10, every narrow tier K_WIDE at an invoke into slot 56 or
+higher -- together with deep_keys.
+
+Out of these scopes' reach still: T2, the narrow HBM tier and the layered tier
+(reached only by outgrowing T1, which no small history does), mutex4 (no inert
+op: a crashed acquire or release is legal in some state) and table models.
+
 A key the device gets wrong is printed as op maps (Loaded.same)."""
 import time
 
@@ -59,11 +93,14 @@ def dev(**kw) -> Device:
 
 
 class Loaded:
-    """A scope, packed, with its oracle records; prep times in .prep (s)."""
+    """A scope -- or, with n_inert and place, small_scope.widened of it --
+    packed, with its oracle records; prep times in .prep (s)."""
 
-    def __init__(self, name):
+    def __init__(self, name, n_inert=0, place=None):
         t0 = time.perf_counter()
-        self.b = SS.scope(name)
+        self.b = SS.widened(SS.scope(name), n_inert, place) if n_inert else SS.scope(name)
+        self.scope_name, self.n_inert, self.place = name, n_inert, place
+        name = f"{name} + {n_inert} {place}" if n_inert else name
         self.name, self.model, self.mdl = name, self.b.scope.model, self.b.scope.model_obj()
         t1 = time.perf_counter()
         self.pk = Packed(self.b.hist, self.mdl)
@@ -80,6 +117,7 @@ class Loaded:
         assert not self.pk.view.trans_off  # one state numbering for the batch (state_values)
         self._batches = {}
         self._finals = None
+        self.width = np.ctypeslib.as_array(self.pk.view.key_width, shape=(self.pk.n_keys,))
 
     def oracle(self, budget):
         if budget not in self._orc:
@@ -136,23 +174,31 @@ class Loaded:
                     mask = 0
                     for q in L:
                         mask |= 1 << a.final_slots[q]
-                    recs.add((mask, ids[oracle_state_value(st, self.model)] << 48))
+                    # (lo = slots 0..63, hi = slots 64..111 | state << 48: helpers.encode_finals)
+                    recs.add((mask & ((1 << 64) - 1), mask >> 64 | ids[oracle_state_value(st, self.model)] << 48))
                 assert len(recs) == len(a.final_configs) <= 10
                 self._finals[k] = recs
         return self._finals
 
 
 _loaded = {}
+KEEP_WIDENED = 3  # widened scopes kept at once (cas4p2 + 11 is 5.3 M rows): the tests below use them in groups
 
 
 @pytest.fixture(scope="module")
 def scopes():
-    def load(name) -> Loaded:
-        if name not in _loaded:
-            _loaded[name] = Loaded(name)
-        return _loaded[name]
+    def load(name, n_inert=0, place=None) -> Loaded:
+        key = (name, n_inert, place)
+        if key not in _loaded:
+            wide = [k for k in _loaded if k[1]]
+            if n_inert and len(wide) >= KEEP_WIDENED:
+                del _loaded[wide[0]]
+            _loaded[key] = Loaded(name, n_inert, place)
+        return _loaded[key]
     yield load
     _loaded.clear()
+    _one.clear()
+    _expect.clear()
     _devs.clear()
     SS.scope.cache_clear()
 
@@ -343,12 +389,11 @@ def test_wgl(scopes, name, budget, path_flags):
         assert (orc["valid"] == -1).any()  # the budget is met, on every scope
 
 
-@pytest.mark.parametrize("name", SS.ORDER)
-def test_competition(scopes, name):
+def competition_same(L):
     """test_gpu_wgl.test_competition_answers_budget_keys_with_wgl's rule at a
     budget of 1: :linear's record where it has one, WGL's verdict (analyzer
     :wgl) for the keys :linear gives up on at the budget."""
-    L = scopes(name)
+    name = L.name
     budget = 1
     lin = L.oracle(budget)
     _, wgl, _, _ = cref.check_history_wgl(L.b.hist.as_c(), budget=budget, threads=8, model=L.model)
@@ -364,6 +409,11 @@ def test_competition(scopes, name):
         bad = np.flatnonzero(getattr(r, f) != want)
         assert not len(bad), (f"{name}, competition: {f} differs on {len(bad)} keys; device {getattr(r, f)[bad[0]]}, "
                               f"oracles {want[bad[0]]} on {L.b.describe(int(bad[0]))}")
+
+
+@pytest.mark.parametrize("name", SS.ORDER)
+def test_competition(scopes, name):
+    competition_same(scopes(name))
 
 
 # ---------------------------------------------------------------- (g)
@@ -477,3 +527,356 @@ def test_row_order(merged):
     same_finals("round robin against key-major", r, one)
     r = dev().check(pk, verdicts_only=True)
     L.same(f"round robin, default, path {r.stats['t0_path']}", r)
+
+
+# ---------------------------------------------------------------- (j) .. (n): the set tiers
+# small_scope.widened: 11 inert ops put every key past the register tier's 10
+# pending ops, 62 past the narrow config's 56 window slots; the records stay
+# the unwidened key's (tests/test_small_scope.py), the oracle here is cref on
+# the widened history itself.
+T0_MAX_WIDTH = 10          # lattice_core.hpp: a key_width above it is K_SPILL before the first event
+DIRECT_T3_WIDTH = 28       # device_search.hpp LC_DIRECT_T3_WIDTH: wider keys skip T1 / T2
+NARROW_MAX_SLOTS = 56      # an :invoke with a window slot >= 56 is K_WIDE in every narrow tier
+# The wide tier's per-block workspace is sized from the budget (ensure_ws):
+# 2^20 would reserve tables for a million configs a block where every set here
+# has at most 11 (|I| at most 12: leg (e)).  4096 is a power of two far above
+# both and small for the workspace; the oracle runs at the same budget.
+WIDE_BUDGET = 4096
+WIDE_SCOPES = ("cas2", "cas3", "cas4p2", "reg4")
+
+
+def took(what, L, t0):
+    print(f"{L.name}, {what}: {L.pk.n_keys} keys, {time.perf_counter() - t0:.2f} s")
+
+
+def in_t1(L, r, what):
+    """The set tier T1 answered every key: none fits the register tier (its
+    kernels return K_SPILL on key_width alone), none is wide enough to skip
+    T1, every key was finished (lc_stats.lds_keys, which Device.check names
+    keys_done, counts the keys finished in any tier) and none was handed past
+    T2 (deep_keys)."""
+    assert L.width.min() > T0_MAX_WIDTH and L.width.max() <= DIRECT_T3_WIDTH, what
+    print(f"{L.name}, {what}: keys_done {r.stats['keys_done']}, deep_keys {r.stats['deep_keys']}, t0_path {r.stats['t0_path']}")
+    assert r.stats["keys_done"] == L.pk.n_keys and r.stats["deep_keys"] == 0, what
+
+
+def in_wide(L, r, what):
+    """The wide HBM tier answered every key: every key's window passes slot
+    55, where each narrow tier returns K_WIDE, and all of them went to the
+    HBM tier (deep_keys)."""
+    assert L.width.min() > NARROW_MAX_SLOTS and L.width.max() <= 112, what
+    print(f"{L.name}, {what}: keys_done {r.stats['keys_done']}, deep_keys {r.stats['deep_keys']}, t3_bytes {r.stats['t3_bytes']}")
+    assert r.stats["deep_keys"] == L.pk.n_keys and r.stats["keys_done"] == L.pk.n_keys, what
+
+
+def finals_same(L, r, what, want=None):
+    """n_final and the records of every invalid key, both words, against
+    linear_ref.analysis on the widened ops (want: against those records).  (A
+    key of two ops fails with no pending op linearized, so cas2's masks are all
+    0 and its records differ by state alone.)"""
+    want = L.oracle_finals() if want is None else want
+    assert len(want) == L.b.scope.invalid
+    fin = r.final.tolist()
+    for k, recs in want.items():
+        assert r.n_final[k] == len(recs), f"{what}: {L.b.describe(k)}"
+        assert {tuple(x) for x in fin[k][:len(recs)]} == recs, f"{what}: {L.b.describe(k)}\n{L.b.ops(k)}"
+
+
+def shifted_finals(L0, L):
+    """The final configs of a scope widened at `head`, from the unwidened
+    scope's (Loaded.oracle_finals, linear_ref.analysis): the inert invokes come
+    first and hold slots 0 .. n_inert - 1 for good, so every live op has its
+    unwidened slot + n_inert (tests/test_small_scope.py asserts it from the
+    packed words of every key) and a config its unwidened mask << n_inert, with
+    the same register value.  Returns the records and the highest bit set."""
+    assert L.place == "head"
+    n = L.n_inert
+    value = L0.state_values()
+    ids = {v: s for s, v in enumerate(L.state_values())}
+    out, top = {}, 0
+    for k, recs in L0.oracle_finals().items():
+        out[k] = set()
+        for lo, hi in recs:
+            assert hi & MASK48 == 0
+            mask = lo << n
+            top = max(top, mask.bit_length())
+            out[k].add((mask & ((1 << 64) - 1), mask >> 64 | ids[value[hi >> 48]] << 48))
+        assert len(out[k]) == len(recs)
+    return out, top
+
+
+def budget_leg(L, r, budget, what):
+    """Leg (e)'s assertions at one budget; returns the oracle's unknown keys."""
+    orc = L.oracle(budget)
+    L.same(what, r, peak=True, budget=budget)
+    unknown = orc["valid"] == -1
+    assert (r.cause[r.valid == -1] == BUDGET_CAUSE).all() and (unknown == (orc["cause"] == BUDGET_CAUSE)).all()
+    assert (r.fail_event[unknown] >= 0).all()
+    return unknown
+
+
+# ---------------------------------------------------------------- (j)
+@pytest.mark.parametrize("place", SS.PLACES)
+@pytest.mark.parametrize("name", WIDE_SCOPES)
+def test_t1(scopes, name, place):
+    L = scopes(name, 11, place)
+    K = L.pk.n_keys
+    t0 = time.perf_counter()
+    d = dev(count_probes=True)
+    r = d.check(L.pk)
+    in_t1(L, r, "T1")
+    L.same("T1, probes counted", r, peak=True)
+    assert r.stats["probes"] == int(L.orc["probes"].sum())
+    if place == "mid":
+        x = d.check(L.pk, verdicts_only=True)
+        in_t1(L, x, "T1, verdicts only")
+        L.same("T1, verdicts only", x)
+        x = d.check(L.pk, peaks=False)
+        in_t1(L, x, "T1, no peaks")
+        L.same("T1, no peaks", x)
+        same_finals(f"{L.name}, T1, no peaks", x, r, ordered=False)
+    if name == "cas3" and place == "mid":
+        dn = dev()
+        db = dn.upload(L.pk)
+        db.check_node(K)
+        L.same("T1, upload + check_node", Records(dn.node_records(K)))
+    if name == "cas2" and place != "mid":
+        finals_same(L, r, "T1")
+    if name == "cas3" and place == "head":  # configs with pending ops linearized: slot bits 11 .. 13
+        want, top = shifted_finals(scopes("cas3"), L)
+        assert top == 11 + 3
+        finals_same(L, r, "T1, against the unwidened configs << 11", want)
+    took("T1", L, t0)
+
+
+@pytest.mark.parametrize("budget", [1, 2, 3, 5, 12])
+def test_t1_budgets(scopes, budget):
+    L = scopes("cas3", 11, "mid")
+    t0 = time.perf_counter()
+    r = dev(budget=budget).check(L.pk)
+    in_t1(L, r, f"T1, budget {budget}")
+    unknown = budget_leg(L, r, budget, f"T1, budget {budget}")
+    assert unknown.any() if budget == 1 else not unknown.any() if budget == 12 else True
+    took(f"T1, budget {budget}", L, t0)
+
+
+# ---------------------------------------------------------------- (k)
+WIDE_RUNS = [("cas2", p) for p in SS.PLACES] + [("cas3", "head"), ("cas3", "tail"), ("reg4", "head")]
+
+
+@pytest.mark.parametrize("name,place", WIDE_RUNS)
+def test_wide_hbm(scopes, name, place):
+    L = scopes(name, 62, place)
+    t0 = time.perf_counter()
+    orc = L.oracle(WIDE_BUDGET)
+    assert not (orc["valid"] == -1).any()
+    r = dev(count_probes=True, budget=WIDE_BUDGET).check(L.pk)
+    in_wide(L, r, "wide HBM tier")
+    L.same("wide HBM tier", r, peak=True, budget=WIDE_BUDGET)
+    assert r.stats["probes"] == int(orc["probes"].sum())
+    if name == "cas2" and place != "mid":
+        finals_same(L, r, "wide HBM tier")
+    if name == "cas3" and place == "head":  # slot bits 62 .. 64: both words of a wide config
+        want, top = shifted_finals(scopes("cas3"), L)
+        assert top == 62 + 3
+        finals_same(L, r, "wide HBM tier, against the unwidened configs << 62", want)
+    took("wide HBM tier", L, t0)
+
+
+@pytest.mark.parametrize("budget", [1, 2, 3])
+def test_wide_hbm_budgets(scopes, budget):
+    L = scopes("cas2", 62, "head")
+    t0 = time.perf_counter()
+    r = dev(budget=budget).check(L.pk)
+    in_wide(L, r, f"wide HBM tier, budget {budget}")
+    unknown = budget_leg(L, r, budget, f"wide HBM tier, budget {budget}")
+    assert unknown.any() or budget > 1
+    took(f"wide HBM tier, budget {budget}", L, t0)
+
+
+# ---------------------------------------------------------------- (l)
+@pytest.mark.parametrize("name,n_inert,place", [("cas2", 11, "head"), ("cas2", 62, "head"), ("cas3", 11, "mid")])
+def test_wgl_widened(scopes, name, n_inert, place):
+    L = scopes(name, n_inert, place)
+    for budget, path_flags in ((1 << 20, 0), (3, 0), (1 << 20, N.LC_PATH_WGL_EV_HBM)):
+        t0 = time.perf_counter()
+        _, orc = wgl_same(L, budget, path_flags)
+        if budget == 1 << 20:
+            sc = L.b.scope
+            assert ((orc["valid"] == 1).sum(), (orc["valid"] == 0).sum()) == (sc.valid, sc.invalid)
+        took(f"wgl, budget {budget}, path_flags {path_flags:#x}", L, t0)
+
+
+def test_competition_widened(scopes):
+    L = scopes("cas3", 11, "mid")
+    t0 = time.perf_counter()
+    competition_same(L)
+    took("competition, budget 1", L, t0)
+
+
+# ---------------------------------------------------------------- (m), (n)
+# A set record is STREAM_SET_REC_WORDS * 4 = 524,608 bytes and the pool grows
+# by chunks of 4 << c slots: a stream in which 2,048 keys migrate holds at most
+# 4,092 slots, 2.15 GB; all of cas3 at once would be about 49 GB.
+STREAM_BATCH = 2048
+_one, _expect = {}, {}
+
+
+def one_shot(L):
+    """The one-shot T1 records of a scope + 11, and every invalid key's final
+    configs with register values for state ids (as the fixture `merged`)."""
+    if L.name not in _one:
+        one = dev(count_probes=True).check(L.pk)
+        in_t1(L, one, "one shot")
+        L.same("one shot", one, peak=True)
+        sv = [-1 if v is None else v for v in L.state_values()]
+        one.by_value = {k: sorted((lo, hi & MASK48, sv[hi >> 48]) for lo, hi in one.final[k, :one.n_final[k]].tolist())
+                        for k in np.flatnonzero(L.orc["valid"] == 0).tolist()}
+        _one[L.name] = one
+    return _one[L.name]
+
+
+def stream_expect(L, lo, hi):
+    """Keys lo .. hi, one row of each in turn, and from stream_helpers.Restated
+    on those rows: the append that decides each invalid key's failing :ok
+    (n_calls: finish), each key's defer_at and event count."""
+    if (L.name, lo, hi) not in _expect:
+        rr = L.b.round_robin(lo, hi)
+        rs = S.Restated(rr, 0)
+        assert rs.keys == list(range(lo, hi)) and not rs.error
+        orc, step = L.orc[lo:hi], hi - lo
+        bad = np.flatnonzero(orc["valid"] == 0)
+        ready = np.array([rs.ready[lo + int(k)][int(orc["fail_event"][k])] for k in bad], np.int64)
+        row = np.array([rs.events[lo + int(k)][int(orc["fail_event"][k])][3] for k in bad], np.int64)
+        n_calls = -(-len(rr) // step)
+        due = np.where(ready >= S.NEVER, n_calls, (np.minimum(ready, len(rr)) - 1) // step)
+        assert (due[ready == row + 1] == row[ready == row + 1] // step).all()
+        defer_at = np.array([rs.defer_at[k] for k in range(lo, hi)], np.int64)
+        n_ev = np.array([len(rs.events[k]) for k in range(lo, hi)], np.int64)
+        assert (defer_at >= 0).all()  # every key takes window slot 10 in its inert block
+        _expect[L.name, lo, hi] = (rr, n_calls, bad, due, defer_at, n_ev)
+    return _expect[L.name, lo, hi]
+
+
+def stream_leg(L, lo, hi, exact, set_tier, one=None):
+    """One stream over keys lo .. hi, appended as many rows at a time as it has
+    keys; test_stream's assertions, and where each key was searched."""
+    rr, n_calls, bad, due, defer_at, n_ev = stream_expect(L, lo, hi)
+    K, step, orc = hi - lo, hi - lo, L.orc[lo:hi]
+    what = f"{L.name}, keys {lo}..{hi}, stream exact={exact} set_tier={set_tier}"
+    # alive when its migrating invoke is searched: valid, or failing at or after it
+    reaches = (orc["valid"] != 0) | (orc["fail_event"].astype(np.int64) >= defer_at)
+    if not set_tier:  # past the register tier a key waits for finish
+        due = np.where(reaches[bad], n_calls, due)
+    s = Stream(dev(), L.mdl, set_tier=set_tier, exact=exact)
+    try:
+        reported = {}
+
+        def after(n_rows, up):
+            call = (n_rows - 1) // step
+            for i in up.invalid:
+                assert i not in reported, f"{what}: key {lo + i} reported twice"
+                reported[i] = call
+
+        S.feed(s, rr, step, after)
+        up = s.finish()
+        for i in up.invalid:
+            assert i not in reported, f"{what}: key {lo + i} reported twice"
+            reported[i] = n_calls
+        assert s.keys == list(range(lo, hi))
+        got = np.array([reported.get(int(k), -1) for k in bad])
+        wrong = np.flatnonzero(got != due)
+        assert not len(wrong), (f"{what}: {len(wrong)} keys reported in another call: call {got[wrong[0]]}, due "
+                                f"{due[wrong[0]]} ({n_calls}: finish) on {L.b.describe(lo + int(bad[wrong[0]]))}")
+        assert set(reported) == set(bad.tolist()), f"{what}: a valid key was reported"
+        t = s.tiers()
+        tier = [s.key_tier(i) for i in range(K)]
+        assert sum(t.values()) == K and all(t[name] == tier.count(name) for name in t)
+        if set_tier:
+            assert up.n_deferred == 0 and t["fallen_back"] == 0, f"{what}: {up}, {t}"
+            at = np.array([s.key_events(i)["deferred_at"] for i in range(K)], np.int64)
+            moved = np.flatnonzero(reaches & (defer_at < n_ev - 1))
+            wrong = [int(i) for i in moved if tier[i] not in ("set", "dead") or at[i] != defer_at[i]]
+            assert not wrong, (f"{what}: {len(wrong)} keys not in the set tier: tier {tier[wrong[0]]}, deferred_at "
+                               f"{at[wrong[0]]}, expected {defer_at[wrong[0]]} on {L.b.describe(lo + wrong[0])}")
+            # every invalid key is dead, every valid one that migrated is still in the set tier
+            assert t["dead"] == len(bad) and t["set"] >= int((orc["valid"][moved] == 1).sum())
+            st = s.set_stats()
+            assert st["pool_in_use"] == t["set"] and st["pool_peak"] >= t["set"]
+        else:
+            # The packer counts a key as deferred when it emits the invoke that takes slot 10
+            # (host_stream.cpp drain), and every key's rows hold one.  A key is dead iff it was
+            # reported online, before that invoke; every other key is checked at finish.
+            assert up.n_deferred == K, f"{what}: {up}"
+            assert t == {"register": 0, "set": 0, "fallen_back": int(reaches.sum()), "dead": K - int(reaches.sum())}, t
+            assert s.set_stats()["pool_slots"] == 0
+        res = s.results()
+        L.same(what, res, lo, hi, peak=exact)
+        if exact:
+            np.testing.assert_array_equal(res.n_final, one.n_final[lo:hi])
+            fin_s = res.final[bad].tolist()
+            for k, fin in zip(bad.tolist(), fin_s):
+                want = one.by_value[lo + k]
+                value = {}
+                for _lo, hi_w in fin[:len(want)]:
+                    if hi_w >> 48 not in value:
+                        v = s.state_value(k, hi_w >> 48)
+                        value[hi_w >> 48] = -1 if v is None else v
+                got_k = sorted((lo_w, hi_w & MASK48, value[hi_w >> 48]) for lo_w, hi_w in fin[:len(want)])
+                assert got_k == want, f"{what}: {L.b.describe(lo + k)}"
+        else:
+            assert res.peak is None and res.final is None
+        return dict(t, n_deferred=up.n_deferred, reaches=int(reaches.sum()), online=int((due < n_calls).sum()),
+                    at_finish=int((due == n_calls).sum()))
+    finally:
+        s.close()
+
+
+MODES = [(False, True), (True, True)]
+MODE_IDS = ["set_tier", "exact+set_tier"]
+
+
+@pytest.mark.parametrize("exact,set_tier", MODES, ids=MODE_IDS)
+@pytest.mark.parametrize("place", SS.PLACES)
+def test_stream_set_cas2(scopes, place, exact, set_tier):
+    """cas2 + 11, all 2,119 keys in one stream: every key migrates
+    (k_stream_migrate) and is searched on in the resident set tier
+    (k_stream_set, exact: k_stream_set_exact)."""
+    L = scopes("cas2", 11, place)
+    t0 = time.perf_counter()
+    got = stream_leg(L, 0, L.pk.n_keys, exact, set_tier, one_shot(L) if exact else None)
+    assert got["online"] > 100
+    print(got)
+    took(f"stream exact={exact} set_tier={set_tier}", L, t0)
+
+
+@pytest.mark.parametrize("exact,set_tier", MODES, ids=MODE_IDS)
+def test_stream_set_cas3(scopes, exact, set_tier):
+    """cas3 + 11 mid, all 93,367 keys, 2,048 keys a stream (the pool's memory:
+    STREAM_BATCH), each stream closed before the next opens."""
+    L = scopes("cas3", 11, "mid")
+    K = L.pk.n_keys
+    one = one_shot(L) if exact else None
+    t0 = time.perf_counter()
+    total = {}
+    for lo in range(0, K, STREAM_BATCH):
+        got = stream_leg(L, lo, min(K, lo + STREAM_BATCH), exact, set_tier, one)
+        for k, v in got.items():
+            total[k] = total.get(k, 0) + v
+    print(total)
+    assert total["dead"] == L.b.scope.invalid and total["fallen_back"] == 0
+    assert total["online"] > 10_000 and total["at_finish"] > 1_000
+    took(f"stream exact={exact} set_tier={set_tier}, {-(-K // STREAM_BATCH)} streams", L, t0)
+
+
+@pytest.mark.parametrize("exact", [False, True], ids=["plain", "exact"])
+def test_stream_without_the_set_tier(scopes, exact):
+    """cas2 + 11 mid with the set tier off: a key whose failing :ok is decided
+    before its inert block is reported online, every other key waits for
+    `finish` and is answered there through the batch path."""
+    L = scopes("cas2", 11, "mid")
+    t0 = time.perf_counter()
+    got = stream_leg(L, 0, L.pk.n_keys, exact, False, one_shot(L) if exact else None)
+    print(got)
+    assert got["online"] > 100 and got["at_finish"] > 100
+    took(f"stream exact={exact} set_tier=False", L, t0)
