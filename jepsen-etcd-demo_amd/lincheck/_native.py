@@ -452,6 +452,31 @@ QUEUE_SIGNATURES = {
     "lc_queue_hist_free": (None, [C.c_void_p]),
 }
 
+# ---- streaming total-queue and unique-ids (include/lincheck_queue_stream.h; ABI 13, additive) ----
+# A header and a table of their own: QUEUE_SIGNATURES mirrors include/lincheck_queue.h name for name.
+
+
+class LcQueueStreamOpts(C.Structure):
+    _fields_ = [("slots", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LcQueueStreamUpdate(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("rows", C.c_int64), ("packed", C.c_int64), ("distinct", C.c_int64),
+                ("slots", C.c_int64), ("grew", C.c_int64), ("n_changed", C.c_int64), ("changed", P(C.c_int64))]
+
+
+QUEUE_STREAM_SIGNATURES = {
+    "lc_queue_stream_open": (C.c_int, [C.c_void_p, C.c_uint32, P(LcQueueStreamOpts), P(C.c_void_p)]),
+    "lc_queue_stream_append": (C.c_int, [C.c_void_p, P(LcQueueHistory), P(LcQueueStreamUpdate)]),
+    "lc_queue_stream_counts": (C.c_int, [C.c_void_p, P(C.c_int8), P(C.c_uint64), P(C.c_int64), P(C.c_int64), P(C.c_uint8)]),
+    "lc_queue_stream_results": (C.c_int, [C.c_void_p, P(LcQueueResult)]),
+    "lc_queue_stream_keys": (C.c_int64, [C.c_void_p, P(C.c_int64)]),
+    "lc_queue_stream_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_queue_stream_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_queue_stream_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_queue_stream_close": (None, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -468,7 +493,7 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
-        tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES)
+        tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES, QUEUE_STREAM_SIGNATURES)
         for name, (res, args) in [item for t in tables for item in t.items()]:
             fn = getattr(L, name)
             fn.restype = res

@@ -800,7 +800,8 @@ def total_queue(opts: Optional[Dict] = None):
     """jepsen.checker/total-queue: every value's attempted and acknowledged
     enqueues against its dequeues, tallied in a hash table on the device
     (lincheck.queue).  opts: {"slots": a power of two at least the number of
-    values, "host": bool -- lc_queue_check_host's plain fold, no device}."""
+    values, "host": bool -- lc_queue_check_host's plain fold, no device}.
+    .stream(dev) checks while the test runs (lincheck.queue_stream)."""
     from .queue import TotalQueueChecker
     return TotalQueueChecker(opts)
 

@@ -384,6 +384,15 @@ class _QueueChecker:
         from . import checker as ck
         return ck.device_for(self.device)
 
+    def stream(self, dev=None):
+        """A streaming check by this checker's rules
+        (lincheck.queue_stream.QueueStream): rows are appended while the test
+        runs, and after every append the results are those of check() on
+        everything appended so far.  {"host": True}: the host stream."""
+        from .queue_stream import QueueStream
+        opts = {"slots": self.slots, "ent-cap": self.ent_cap}
+        return QueueStream(None if self.host else dev if dev is not None else self.dev(), self.mode, opts)
+
     def _check(self, history):
         hist = history if isinstance(history, QueueHistory) else QueueHistory.from_ops(history)
         packed = PackedQueue(hist, self.mode)
