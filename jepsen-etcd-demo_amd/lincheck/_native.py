@@ -477,6 +477,32 @@ QUEUE_STREAM_SIGNATURES = {
     "lc_queue_stream_close": (None, [C.c_void_p]),
 }
 
+# ---- streaming checker/counter (include/lincheck_counter_stream.h; ABI 13, additive) ----
+# A header and a table of their own: COUNTER_SIGNATURES mirrors include/lincheck_counter.h name for name.
+
+
+class LcCounterStreamOpts(C.Structure):
+    _fields_ = [("tile", C.c_uint32), ("reads", C.c_uint32), ("launch_events", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class LcCounterStreamUpdate(C.Structure):
+    _fields_ = [("n_keys", C.c_int64), ("rows", C.c_int64), ("events", C.c_int64), ("reads", C.c_int64),
+                ("reads_total", C.c_int64), ("patched", C.c_int64), ("revisited", C.c_int64), ("grew", C.c_int64),
+                ("n_changed", C.c_int64), ("changed", P(C.c_int64))]
+
+
+COUNTER_STREAM_SIGNATURES = {
+    "lc_counter_stream_open": (C.c_int, [C.c_void_p, P(LcCounterStreamOpts), P(C.c_void_p)]),
+    "lc_counter_stream_append": (C.c_int, [C.c_void_p, P(LcCounterHistory), P(LcCounterStreamUpdate)]),
+    "lc_counter_stream_counts": (C.c_int, [C.c_void_p, P(C.c_int8), P(C.c_uint64), P(C.c_uint64)]),
+    "lc_counter_stream_results": (C.c_int, [C.c_void_p, P(LcCounterResult), P(C.c_int64)]),
+    "lc_counter_stream_keys": (C.c_int64, [C.c_void_p, P(C.c_int64)]),
+    "lc_counter_stream_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_counter_stream_last_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_counter_stream_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_counter_stream_close": (None, [C.c_void_p]),
+}
+
 _lib: Optional[C.CDLL] = None
 
 
@@ -493,7 +519,8 @@ def lib() -> C.CDLL:
         if not os.path.exists(LIB_PATH):
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
-        tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES, QUEUE_STREAM_SIGNATURES)
+        tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES, QUEUE_STREAM_SIGNATURES,
+                  COUNTER_STREAM_SIGNATURES)
         for name, (res, args) in [item for t in tables for item in t.items()]:
             fn = getattr(L, name)
             fn.restype = res

@@ -791,7 +791,8 @@ def perf(opts: Optional[Dict] = None):
 def counter(opts: Optional[Dict] = None):
     """jepsen.checker/counter: the bounds of every read of a counter, by a
     prefix scan on the device (lincheck.counter).  opts: {"tile": 256 | 2048,
-    "host": bool -- lc_counter_check_host's plain fold, no device}."""
+    "host": bool -- lc_counter_check_host's plain fold, no device}.
+    .stream(dev) checks while the test runs (lincheck.counter_stream)."""
     from .counter import CounterChecker
     return CounterChecker(opts)
 

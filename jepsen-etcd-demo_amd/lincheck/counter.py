@@ -312,6 +312,15 @@ class CounterChecker:
         from . import checker as ck
         return ck.device_for(self.device)
 
+    def stream(self, dev=None):
+        """A streaming check by this checker's rules
+        (lincheck.counter_stream.CounterStream): rows are appended while the
+        test runs, and after every append the results are those of check() on
+        everything appended so far.  {"host": True} or no device: the host
+        stream."""
+        from .counter_stream import CounterStream
+        return CounterStream(None if self.host else dev, {"tile": self.tile, "err-cap": self.err_cap})
+
     def _check(self, history):
         hist = history if isinstance(history, CounterHistory) else CounterHistory.from_ops(history)
         packed = PackedCounter(hist)
