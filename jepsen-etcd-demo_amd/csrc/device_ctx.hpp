@@ -341,6 +341,9 @@ struct Dev {
     lcf::SetFullDev *setfulldev = nullptr;  // lc_setfull_check's (device_setfull.hip), likewise
     CounterDev *counterdev = nullptr;  // lc_counter_check's (device_api.hip), likewise
     QueueDev *queuedev = nullptr;  // lc_queue_check's (device_api.hip), likewise
+    // lc_counter_check_history's (device_counter_pack.hip, in libcounter_pack_kernels.so, which also frees it), likewise
+    void *cpackdev = nullptr;
+    void (*cpackdev_free)(void *) = nullptr;
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
@@ -350,6 +353,7 @@ struct Dev {
         lcf::setfull_dev_free(setfulldev);
         delete counterdev;
         delete queuedev;
+        if (cpackdev_free) cpackdev_free(cpackdev);
         dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
         dfree(peak); dfree(final_cfg); dfree(n_final);

@@ -405,6 +405,22 @@ COUNTER_SIGNATURES = {
     "lc_counter_hist_free": (None, [C.c_void_p]),
 }
 
+# ---- checker/counter from raw rows (include/lincheck_counter_pack.h; ABI 13, additive) ----
+# A header and a table of their own: COUNTER_SIGNATURES mirrors include/lincheck_counter.h name for name.
+COUNTER_PACK_SIGNATURES = {
+    "lc_counter_check_history": (C.c_int, [C.c_void_p, P(LcCounterHistory), P(LcCounterOpts), P(C.c_void_p)]),
+    "lc_counter_checked_free": (None, [C.c_void_p]),
+    "lc_counter_checked_view": (C.c_int, [C.c_void_p, P(LcCounterBatch), P(LcCounterResult)]),
+    "lc_counter_checked_keys": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_counter_checked_key_error": (C.c_char_p, [C.c_void_p, C.c_int64]),
+    "lc_counter_checked_key_error_row": (C.c_int64, [C.c_void_p, C.c_int64]),
+    "lc_counter_checked_read_vals": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_counter_checked_batch": (C.c_int, [C.c_void_p, C.c_void_p, P(LcCounterBatch)]),
+    "lc_counter_history_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_counter_pack_launch_info": (C.c_int, [P(C.c_int64)]),
+    "lc_counter_pack_table_slots": (C.c_int64, [C.c_int64]),
+}
+
 # ---- checker/total-queue and /unique-ids (include/lincheck_queue.h; ABI 13, additive) ----
 LC_QF_ENQUEUE, LC_QF_DEQUEUE, LC_QF_DRAIN, LC_QF_GENERATE, LC_QF_OTHER = 0, 1, 2, 3, 4
 LC_QM_TOTAL_QUEUE, LC_QM_UNIQUE_IDS = 0, 1
@@ -520,7 +536,7 @@ def lib() -> C.CDLL:
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
         tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES, QUEUE_STREAM_SIGNATURES,
-                  COUNTER_STREAM_SIGNATURES)
+                  COUNTER_STREAM_SIGNATURES, COUNTER_PACK_SIGNATURES)
         for name, (res, args) in [item for t in tables for item in t.items()]:
             fn = getattr(L, name)
             fn.restype = res

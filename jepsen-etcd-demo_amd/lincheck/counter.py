@@ -17,6 +17,10 @@ read's two bounds and the ordered indices of the reads out of bounds.  Under
 independent.checker every key is checked in one lc_counter_check call.
 {"host": True} runs lc_counter_check_host instead: the same fold in plain C++
 on one thread, no device (tests, and the timing's baseline).
+{"pack": "device"} takes CounterHistory -> CheckedCounter
+(lc_counter_check_history) instead: the raw columns are uploaded, the device
+groups, pairs and packs them and checks the batch where it lies, and only
+results come back; the result maps are the default path's.
 """
 
 from __future__ import annotations
@@ -46,7 +50,7 @@ class CounterHistory:
         self.type = np.ascontiguousarray(type_, np.uint8)
         self.f = np.ascontiguousarray(f, np.uint8)
         self.n = len(self.type)
-        self.process = np.ascontiguousarray(process, np.int64)
+        self.process = None if process is None else np.ascontiguousarray(process, np.int64)  # None: every row is process 0
         self.key = None if key is None else np.ascontiguousarray(key, np.int64)
         self.value = np.ascontiguousarray(value, np.int64)
         self.index = None if index is None else np.ascontiguousarray(index, np.int64)
@@ -109,7 +113,8 @@ class CounterHistory:
 
     def as_c(self) -> N.LcCounterHistory:
         null64 = C.POINTER(C.c_int64)()
-        return N.LcCounterHistory(self.n, N.ptr(self.type, C.c_uint8), N.ptr(self.f, C.c_uint8), N.ptr(self.process, C.c_int64),
+        return N.LcCounterHistory(self.n, N.ptr(self.type, C.c_uint8), N.ptr(self.f, C.c_uint8),
+                                  null64 if self.process is None else N.ptr(self.process, C.c_int64),
                                   null64 if self.key is None else N.ptr(self.key, C.c_int64), N.ptr(self.value, C.c_int64),
                                   null64 if self.index is None else N.ptr(self.index, C.c_int64))
 
@@ -122,7 +127,8 @@ class CounterHistory:
             v = Tuple(int(self.key[r]), v)
         idx = r if self.index is None or self.index[r] < 0 else int(self.index[r])
         return {"type": TYPE_NAMES[int(self.type[r])], "f": fn, "value": v,
-                "process": "nemesis" if self.process[r] == N.LC_NO_PROCESS else int(self.process[r]), "index": idx}
+                "process": 0 if self.process is None else "nemesis" if self.process[r] == N.LC_NO_PROCESS else int(self.process[r]),
+                "index": idx}
 
     def to_ops(self) -> List[dict]:
         """The rows as op maps again (tests; small histories)."""
@@ -285,7 +291,66 @@ def check_batch(dev, batch: N.LcCounterBatch, tile: int = 0, err_cap: Optional[i
                           dict(upload_ms=ms[0], kernel_ms=ms[1], download_ms=ms[2], total_ms=ms[3]), retried)
 
 
-def result_map(packed: PackedCounter, res: CounterResults, i: int) -> Dict:
+class CheckedCounter:
+    """lc_counter_check_history output: a history packed and checked on the
+    device.  It stands where a PackedCounter stands in result_map, and `res`
+    is the CounterResults of the same call."""
+
+    def __init__(self, dev, hist: CounterHistory, tile: int = 0):
+        self.hist = hist
+        self.dev = dev
+        self._c = hist.as_c()
+        h = C.c_void_p()
+        o = N.LcCounterOpts(int(tile), 0)
+        N.check(N.lib().lc_counter_check_history(dev.handle, C.byref(self._c), C.byref(o), C.byref(h)))
+        self.handle = h
+        v, r = N.LcCounterBatch(), N.LcCounterResult()
+        N.check(N.lib().lc_counter_checked_view(h, C.byref(v), C.byref(r)))
+        K = self.n_keys = int(v.n_keys)
+        keys = np.zeros(max(K, 1), np.int64)
+        N.check(N.lib().lc_counter_checked_keys(h, N.ptr(keys, C.c_int64)))
+        self.keys = [None if k == N.LC_NO_KEY else int(k) for k in keys[:K]]
+        self.status = N.carray(v.status, K, np.uint8)
+        self.ev_off = N.carray(v.ev_off, K + 1, np.uint64)
+        self.read_off = N.carray(v.read_off, K + 1, np.uint64).astype(np.int64)
+        self.n_events = int(self.ev_off[-1])
+        R = self.n_reads = int(self.read_off[-1])
+        self._read_val = np.zeros(max(R, 1), np.int64)
+        N.check(N.lib().lc_counter_checked_read_vals(h, N.ptr(self._read_val, C.c_int64)))
+        self._read_val = self._read_val[:R]
+        ms = (C.c_double * 6)()
+        N.check(N.lib().lc_counter_history_timing(dev.handle, ms))
+        names = ("upload_ms", "group_ms", "build_ms", "kernel_ms", "download_ms", "total_ms")
+        self.res = CounterResults(N.carray(r.valid, K, np.int8), N.carray(r.n_errors, K, np.uint64), N.carray(r.lower, R, np.int64),
+                                  N.carray(r.upper, R, np.int64), N.carray(r.err_off, K + 1, np.uint64),
+                                  N.carray(r.err_idx, int(r.n_err), np.uint64), dict(zip(names, ms)))
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            N.lib().lc_counter_checked_free(h)
+            self.handle = None
+
+    def key_error(self, i: int) -> Optional[str]:
+        msg = N.lib().lc_counter_checked_key_error(self.handle, i)
+        return None if msg is None else msg.decode(errors="replace")
+
+    def key_error_row(self, i: int) -> int:
+        return int(N.lib().lc_counter_checked_key_error_row(self.handle, i))
+
+    def read_val(self) -> np.ndarray:
+        return self._read_val
+
+    def arrays(self) -> Dict[str, np.ndarray]:
+        """The batch the device built, downloaded (lc_counter_checked_batch):
+        PackedCounter.arrays()'s names.  Only for the device's latest check."""
+        v, K = N.LcCounterBatch(), self.n_keys
+        N.check(N.lib().lc_counter_checked_batch(self.dev.handle, self.handle, C.byref(v)))
+        sizes = dict(ev_off=K + 1, ev_kind=self.n_events, ev_val=self.n_events, read_off=K + 1, read_val=self.n_reads, status=K)
+        return {name: N.carray(getattr(v, name), sizes[name], dt) for name, dt in BATCH_ARRAYS}
+
+
+def result_map(packed, res: CounterResults, i: int) -> Dict:
     """jepsen.checker/counter's result map of packed key i."""
     if packed.status[i] != N.LC_COUNTER_KEY_OK:
         return {"valid?": "unknown", "error": packed.key_error(i) or "error"}
@@ -305,6 +370,11 @@ class CounterChecker:
         self.tile = int(opts.get("tile", 0))
         self.host = bool(opts.get("host", False))  # lc_counter_check_host: no device
         self.err_cap = opts.get("err-cap")         # tests: the first err_idx capacity
+        self.pack = opts.get("pack", "host")       # "device": lc_counter_check_history packs on the device
+        if self.pack not in ("host", "device"):
+            raise ValueError(f'counter: "pack" is "host" or "device", not {self.pack!r}')
+        if self.pack == "device" and self.host:
+            raise ValueError('counter: {"pack": "device"} runs on the device; it cannot go with {"host": True}')
 
     def dev(self):
         if self.host:
@@ -323,6 +393,9 @@ class CounterChecker:
 
     def _check(self, history):
         hist = history if isinstance(history, CounterHistory) else CounterHistory.from_ops(history)
+        if self.pack == "device":
+            checked = CheckedCounter(self.dev(), hist, self.tile)
+            return checked, checked.res
         packed = PackedCounter(hist)
         return packed, check_batch(self.dev(), packed.view, self.tile, self.err_cap, self.host)
 
