@@ -344,6 +344,10 @@ struct Dev {
     // lc_counter_check_history's (device_counter_pack.hip, in libcounter_pack_kernels.so, which also frees it), likewise
     void *cpackdev = nullptr;
     void (*cpackdev_free)(void *) = nullptr;
+    // lc_perf_check_history's (device_perf_pack.hip, in libperf_pack_kernels.so, which also frees it), likewise; the batch
+    // it builds lies in perfdev's record columns
+    void *ppackdev = nullptr;
+    void (*ppackdev_free)(void *) = nullptr;
     ~Dev() {
         (void)hipSetDevice(device);
         if (stream) (void)hipStreamSynchronize(stream);
@@ -354,6 +358,7 @@ struct Dev {
         delete counterdev;
         delete queuedev;
         if (cpackdev_free) cpackdev_free(cpackdev);
+        if (ppackdev_free) ppackdev_free(ppackdev);
         dfree(lists); dfree(ctl);
         if (hctl) (void)hipHostFree(hctl);
         dfree(peak); dfree(final_cfg); dfree(n_final);

@@ -39,6 +39,11 @@
 // Every record is checked (type, f ids, times inside the batch's bounds) before
 // it addresses a table; a bad one counts nowhere, leaves its row in the error
 // word, and the call returns LC_E_INVALID.
+//
+// The step has two entries over one body (perf_run): perf_check uploads the
+// batch's three columns; perf_check_device runs the same launches on a batch
+// that lc_perf_check_history (device_perf_pack.hip) has written into the
+// device's own columns.
 
 #include <hip/hip_runtime.h>
 
@@ -56,6 +61,12 @@
         hipError_t _e = (expr);                                                            \
         if (_e != hipSuccess)                                                              \
             return lc::fail(LC_E_DEVICE, "%s failed: %s", #expr, hipGetErrorString(_e));  \
+    } while (0)
+
+#define LCP_CHK(expr)          \
+    do {                       \
+        int _rc = (expr);      \
+        if (_rc) return _rc;   \
     } while (0)
 
 namespace lcp {
@@ -593,7 +604,21 @@ struct PerfDev {
     HostBuf hout;
     hipEvent_t ev[4] = {};
     double ms[4] = {0, 0, 0, 0};
+    uint64_t generation = 0;  // bumped whenever the record columns are about to be rewritten
 };
+
+namespace {
+
+int perf_dev_of(PerfDev **dev) {
+    if (*dev) return LC_OK;
+    PerfDev *d = new (std::nothrow) PerfDev();
+    if (!d) return lc::fail(LC_E_NOMEM, "lc_perf_check: out of memory");
+    *dev = d;  // (owned by the context from here on: a failed event is freed with it)
+    for (hipEvent_t &e : d->ev) HIPCHK(hipEventCreate(&e));
+    return LC_OK;
+}
+
+}  // namespace
 
 void perf_dev_free(PerfDev *d) {
     if (!d) return;
@@ -610,18 +635,42 @@ int perf_last_timing(const PerfDev *d, double *out_ms) {
     return LC_OK;
 }
 
-int perf_check(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r) {
+int perf_records_device(PerfDev **dev, uint64_t n, int64_t **t_comp, int64_t **t_inv, uint32_t **meta) {
+    LCP_CHK(perf_dev_of(dev));
+    PerfDev &D = **dev;
+    D.generation++;
+    HIPCHK(D.t_comp.grow(n * 8));
+    HIPCHK(D.t_inv.grow(n * 8));
+    HIPCHK(D.meta.grow(n * 4));
+    *t_comp = (int64_t *)D.t_comp.p; *t_inv = (int64_t *)D.t_inv.p; *meta = (uint32_t *)D.meta.p;
+    return LC_OK;
+}
+
+uint64_t perf_generation(const PerfDev *d) { return d ? d->generation : 0; }
+
+int perf_records_download(PerfDev *d, hipStream_t stream, uint64_t n, int64_t *t_comp, int64_t *t_inv, uint32_t *meta) {
+    if (!d || d->t_comp.cap < n * 8 || d->t_inv.cap < n * 8 || d->meta.cap < n * 4)
+        return lc::fail(LC_E_INVALID, "lc_perf_checked_records: the device holds no such batch");
+    if (!n) return LC_OK;
+    HIPCHK(hipMemcpyAsync(t_comp, d->t_comp.p, n * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(t_inv, d->t_inv.p, n * 8, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipMemcpyAsync(meta, d->meta.p, n * 4, hipMemcpyDeviceToHost, stream));
+    HIPCHK(hipStreamSynchronize(stream));
+    return LC_OK;
+}
+
+namespace {
+
+// lc_perf_check's step.  resident: the record columns already lie in the
+// device's own arrays (perf_records_device), b's column pointers are not read
+// and nothing is uploaded.
+int perf_run(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r, bool resident) {
     lc::Range range("lc_perf_check");
     const auto wall0 = std::chrono::steady_clock::now();
     // everything the host can check, before any kernel
-    if (o->n_q < 1 || o->n_q > LC_PERF_MAX_Q) return lc::fail(LC_E_INVALID, "lc_perf_check: n_q %d is not in 1..%d", o->n_q, LC_PERF_MAX_Q);
-    for (int j = 0; j < o->n_q; ++j)
-        if (!(o->q[j] >= 0.0 && o->q[j] <= 1.0)) return lc::fail(LC_E_INVALID, "lc_perf_check: quantile %d is not in [0, 1]", j);
-    if (b->n_f > LC_PERF_MAX_F)
-        return lc::fail(LC_E_UNSUPPORTED, "lc_perf_check: %d distinct :f, at most %d are supported", b->n_f, LC_PERF_MAX_F);
     int64_t shape[4];
-    if (int rc = lc_perf_shape(b, o, shape)) return rc;
-    if (b->n > 0 && (!b->t_comp || !b->t_inv || !b->meta)) return lc::fail(LC_E_INVALID, "lc_perf_check: null record column");
+    if (int rc = perf_opts_check(b, o, shape)) return rc;
+    if (!resident && b->n > 0 && (!b->t_comp || !b->t_inv || !b->meta)) return lc::fail(LC_E_INVALID, "lc_perf_check: null record column");
     if (b->n > 0 && b->n_f < 1) return lc::fail(LC_E_INVALID, "lc_perf_check: records but no :f names");
     if ((uint64_t)b->n > 0xFFFFFFFFull * 256) return lc::fail(LC_E_INVALID, "lc_perf_check: too many records for one call");
     const uint64_t F = (uint64_t)b->n_f, nr = (uint64_t)shape[1], nq = (uint64_t)shape[3], n_q = (uint64_t)o->n_q;
@@ -641,16 +690,17 @@ int perf_check(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const 
         return lc::fail(LC_E_NOMEM, "lc_perf_check: the digit histograms of %llu groups pass %llu bytes",
                         (unsigned long long)slots_cap, (unsigned long long)PERF_HIST_MAX_BYTES);
 
-    if (!*dev) {
-        *dev = new (std::nothrow) PerfDev();
-        if (!*dev) return lc::fail(LC_E_NOMEM, "lc_perf_check: out of memory");
-        for (hipEvent_t &e : (*dev)->ev) HIPCHK(hipEventCreate(&e));
-    }
+    LCP_CHK(perf_dev_of(dev));
     PerfDev &D = **dev;
     const uint64_t n = (uint64_t)b->n;
-    HIPCHK(D.t_comp.grow(n * 8));
-    HIPCHK(D.t_inv.grow(n * 8));
-    HIPCHK(D.meta.grow(n * 4));
+    if (!resident) {
+        D.generation++;
+        HIPCHK(D.t_comp.grow(n * 8));
+        HIPCHK(D.t_inv.grow(n * 8));
+        HIPCHK(D.meta.grow(n * 4));
+    } else if (D.t_comp.cap < n * 8 || D.t_inv.cap < n * 8 || D.meta.cap < n * 4) {
+        return lc::fail(LC_E_INVALID, "lc_perf_check: the device holds no batch of %llu records", (unsigned long long)n);
+    }
     // out: control words, rate, group, quantiles
     const size_t o_ctl = 0, o_rate = CTL_WORDS * 8, o_group = o_rate + R * 8, o_quant = o_group + G * 8;
     const size_t out_bytes = o_quant + G * n_q * 8;
@@ -665,9 +715,11 @@ int perf_check(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const 
     HIPCHK(D.state.grow(slots_cap * n_q * sizeof(SelState)));
 
     HIPCHK(hipEventRecord(D.ev[0], stream));
-    HIPCHK(hipMemcpyAsync(D.t_comp.p, b->t_comp, n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(D.t_inv.p, b->t_inv, n * 8, hipMemcpyHostToDevice, stream));
-    HIPCHK(hipMemcpyAsync(D.meta.p, b->meta, n * 4, hipMemcpyHostToDevice, stream));
+    if (!resident) {
+        HIPCHK(hipMemcpyAsync(D.t_comp.p, b->t_comp, n * 8, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(D.t_inv.p, b->t_inv, n * 8, hipMemcpyHostToDevice, stream));
+        HIPCHK(hipMemcpyAsync(D.meta.p, b->meta, n * 4, hipMemcpyHostToDevice, stream));
+    }
     HIPCHK(hipEventRecord(D.ev[1], stream));
     HIPCHK(hipMemsetAsync(D.out.p, 0, out_bytes, stream));
     if (slots_cap) HIPCHK(hipMemsetAsync(D.hist.p, 0, slots_cap * n_q * PERF_DIGITS * 4, stream));
@@ -733,6 +785,16 @@ int perf_check(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const 
     if (G) std::memcpy(r->quant, ho + o_quant, G * n_q * 8);
     D.ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - wall0).count();
     return LC_OK;
+}
+
+}  // namespace
+
+int perf_check(PerfDev **dev, hipStream_t stream, const lc_perf_batch *b, const lc_perf_opts *o, lc_perf_result *r) {
+    return perf_run(dev, stream, b, o, r, false);
+}
+
+int perf_check_device(PerfDev **dev, hipStream_t stream, const lc_perf_batch *sizes, const lc_perf_opts *o, lc_perf_result *r) {
+    return perf_run(dev, stream, sizes, o, r, true);
 }
 
 }  // namespace lcp

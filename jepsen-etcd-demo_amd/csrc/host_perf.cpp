@@ -180,6 +180,15 @@ extern "C" int lc_perf_shape(const lc_perf_batch *b, const lc_perf_opts *o, int6
     return LC_OK;
 }
 
+int lcp::perf_opts_check(const lc_perf_batch *b, const lc_perf_opts *o, int64_t *shape4) {
+    if (o->n_q < 1 || o->n_q > LC_PERF_MAX_Q) return lc::fail(LC_E_INVALID, "lc_perf_check: n_q %d is not in 1..%d", o->n_q, LC_PERF_MAX_Q);
+    for (int j = 0; j < o->n_q; ++j)
+        if (!(o->q[j] >= 0.0 && o->q[j] <= 1.0)) return lc::fail(LC_E_INVALID, "lc_perf_check: quantile %d is not in [0, 1]", j);
+    if (b->n_f > LC_PERF_MAX_F)
+        return lc::fail(LC_E_UNSUPPORTED, "lc_perf_check: %d distinct :f, at most %d are supported", b->n_f, LC_PERF_MAX_F);
+    return lc_perf_shape(b, o, shape4);
+}
+
 extern "C" int lc_perf_launch_info(int64_t *out4) {
     if (!out4) return lc::fail(LC_E_INVALID, "lc_perf_launch_info: null argument");
     out4[0] = lcp::PERF_WG_RECORDS; out4[1] = lcp::PERF_TILE_BUCKETS; out4[2] = lcp::PERF_LDS_MAX; out4[3] = lcp::PERF_DIGIT_BITS;

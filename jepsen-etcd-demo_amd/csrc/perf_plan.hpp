@@ -138,4 +138,9 @@ inline PerfShape perf_shape(const lc_perf_batch *b, int64_t rate_dt, int64_t q_d
     return s;
 }
 
+// What lc_perf_check refuses before it touches a device, in its order: n_q,
+// the quantiles, n_f, then lc_perf_shape's checks; shape4 as lc_perf_shape's.
+// Defined in host_perf.cpp (it sets the error text).
+int perf_opts_check(const lc_perf_batch *b, const lc_perf_opts *o, int64_t *shape4);
+
 }  // namespace lcp

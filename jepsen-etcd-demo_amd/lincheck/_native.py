@@ -421,6 +421,19 @@ COUNTER_PACK_SIGNATURES = {
     "lc_counter_pack_table_slots": (C.c_int64, [C.c_int64]),
 }
 
+# ---- checker/perf from raw rows (include/lincheck_perf_pack.h; ABI 13, additive) ----
+# A header and a table of their own: SIGNATURES mirrors include/lincheck.h name for name.
+PERF_PACK_SIGNATURES = {
+    "lc_perf_check_history": (C.c_int, [C.c_void_p, P(LcPerfHistory), P(LcPerfOpts), P(C.c_void_p)]),
+    "lc_perf_checked_free": (None, [C.c_void_p]),
+    "lc_perf_checked_view": (C.c_int, [C.c_void_p, P(LcPerfBatch), P(LcPerfResult)]),
+    "lc_perf_checked_info": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_perf_checked_intervals": (C.c_int, [C.c_void_p, P(C.c_int64)]),
+    "lc_perf_checked_records": (C.c_int, [C.c_void_p, C.c_void_p, P(LcPerfBatch)]),
+    "lc_perf_history_timing": (C.c_int, [C.c_void_p, P(C.c_double)]),
+    "lc_perf_pack_launch_info": (C.c_int, [P(C.c_int64)]),
+}
+
 # ---- checker/total-queue and /unique-ids (include/lincheck_queue.h; ABI 13, additive) ----
 LC_QF_ENQUEUE, LC_QF_DEQUEUE, LC_QF_DRAIN, LC_QF_GENERATE, LC_QF_OTHER = 0, 1, 2, 3, 4
 LC_QM_TOTAL_QUEUE, LC_QM_UNIQUE_IDS = 0, 1
@@ -536,7 +549,7 @@ def lib() -> C.CDLL:
             raise ImportError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'`")
         L = C.CDLL(LIB_PATH)
         tables = (SIGNATURES, SETFULL_STREAM_SIGNATURES, COUNTER_SIGNATURES, QUEUE_SIGNATURES, QUEUE_STREAM_SIGNATURES,
-                  COUNTER_STREAM_SIGNATURES, COUNTER_PACK_SIGNATURES)
+                  COUNTER_STREAM_SIGNATURES, COUNTER_PACK_SIGNATURES, PERF_PACK_SIGNATURES)
         for name, (res, args) in [item for t in tables for item in t.items()]:
             fn = getattr(L, name)
             fn.restype = res

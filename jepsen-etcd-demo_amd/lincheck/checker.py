@@ -783,7 +783,8 @@ def set_full(opts: Optional[Dict] = None):
 
 def perf(opts: Optional[Dict] = None):
     """jepsen.checker/perf (etcdemo.clj:166): {"valid?": True}; the series it
-    would plot are computed on the device (lincheck.perf)."""
+    would plot are computed on the device (lincheck.perf).  opts: {"pack":
+    "host" | "device" -- where the rows are paired and packed}."""
     from .perf import PerfChecker
     return PerfChecker(opts)
 

@@ -10,7 +10,9 @@
 
 The path is its own: PerfHistory (lc_perf_history) -> PackedPerf (lc_perf_pack:
 pairing, orphans, nemesis intervals on the host) -> lc_perf_check -> series.
-The rules are stated in DESIGN.md section 3.10.
+The rules are stated in DESIGN.md section 3.10.  With {"pack": "device"} the
+rows are paired and packed on the device as well (CheckedPerf:
+lc_perf_check_history); the series are the same.
 """
 
 from __future__ import annotations
@@ -157,6 +159,70 @@ class PackedPerf:
                     type=((meta >> 16) & 0xFF).astype(np.uint8))
 
 
+PACKS = ("host", "device")
+
+
+def pack_of(opts: Optional[Dict]) -> str:
+    """The {"pack": ...} option: "host" (the default) or "device"."""
+    pack = (opts or {}).get("pack", "host")
+    if pack not in PACKS:
+        raise ValueError(f'"pack" is "host" or "device", not {pack!r}')
+    return pack
+
+
+class CheckedPerf:
+    """lc_perf_check_history output: what PerfSeries reads from a PackedPerf
+    (names, intervals, the pairing counts, arrays()) and lc_perf_check's tables,
+    from one call that pairs and packs the rows on the device.  arrays()
+    downloads the record columns on first use; the device keeps them only until
+    the context's next perf call."""
+
+    def __init__(self, dev, hist: PerfHistory, opts: Optional[N.LcPerfOpts] = None):
+        self.dev, self.hist = dev, hist
+        self.names = list(hist.names)
+        self._c = hist.as_c()
+        o = opts if opts is not None else make_opts()
+        h = C.c_void_p()
+        N.check(N.lib().lc_perf_check_history(dev.handle, C.byref(self._c), C.byref(o), C.byref(h)))
+        self.handle = h
+        v, r = N.LcPerfBatch(), N.LcPerfResult()
+        N.check(N.lib().lc_perf_checked_view(h, C.byref(v), C.byref(r)))
+        self.view = v
+        self.n = int(v.n)
+        info = np.zeros(4, np.int64)
+        N.check(N.lib().lc_perf_checked_info(h, N.ptr(info, C.c_int64)))
+        self.matched, self.unmatched, self.orphans, n_iv = (int(x) for x in info)
+        iv = np.zeros(max(2 * n_iv, 2), np.int64)
+        N.check(N.lib().lc_perf_checked_intervals(h, N.ptr(iv, C.c_int64)))
+        self.intervals = iv[:2 * n_iv].reshape(n_iv, 2)
+        ms = (C.c_double * 6)()
+        N.check(N.lib().lc_perf_history_timing(dev.handle, ms))
+        F, nr, nq, n_q = int(v.n_f), int(r.rate_n), int(r.q_n), int(o.n_q)
+        self.results = PerfResults(
+            F, tuple(o.q[j] for j in range(n_q)), int(o.rate_dt_ns), int(o.quantile_dt_ns), int(r.rate_first), int(r.q_first),
+            N.carray(r.rate, F * 3 * nr, np.uint64).reshape(F, 3, nr), N.carray(r.group, F * nq, np.uint64).reshape(F, nq),
+            N.carray(r.quant, F * nq * n_q, np.int64).reshape(F, nq, n_q),
+            dict(upload_ms=ms[0], pair_ms=ms[1], build_ms=ms[2], kernel_ms=ms[3], download_ms=ms[4], total_ms=ms[5]))
+        self._arrays = None
+
+    def __del__(self):
+        h = getattr(self, "handle", None)
+        if h:
+            N.lib().lc_perf_checked_free(h)
+            self.handle = None
+
+    def arrays(self) -> Dict[str, np.ndarray]:
+        """Copies of the record columns, as PackedPerf.arrays()."""
+        if self._arrays is None:
+            b = N.LcPerfBatch()
+            N.check(N.lib().lc_perf_checked_records(self.dev.handle, self.handle, C.byref(b)))
+            meta = N.carray(b.meta, self.n, np.uint32)
+            self._arrays = dict(t_comp=N.carray(b.t_comp, self.n, np.int64), t_inv=N.carray(b.t_inv, self.n, np.int64), meta=meta,
+                                f_inv=(meta & 0xFF).astype(np.uint8), f_comp=((meta >> 8) & 0xFF).astype(np.uint8),
+                                type=((meta >> 16) & 0xFF).astype(np.uint8))
+        return self._arrays
+
+
 def batch_of(arrs: Dict[str, Any], n_f: int) -> N.LcPerfBatch:
     """An lc_perf_batch over numpy columns t_comp, t_inv, meta (a caller's own;
     the bounds and the matched count are computed here).  The arrays must
@@ -238,7 +304,7 @@ class PerfSeries:
         points(f, type)  [(t_s, latency_ms)] of every completed op, from the pack
     """
 
-    def __init__(self, packed: PackedPerf, res: PerfResults):
+    def __init__(self, packed, res: PerfResults):
         self.packed, self.res = packed, res
         self.names = packed.names
         self.quantiles: Dict[str, Dict[float, List[Tuple[float, float]]]] = {}
@@ -289,8 +355,13 @@ class PerfSeries:
 
 def analyze(dev, history, opts: Optional[Dict] = None) -> PerfSeries:
     """The perf series of a whole history (a PerfHistory or op maps) on a
-    checker.Device."""
+    checker.Device.  opts["pack"]: "host" (lc_perf_pack, then lc_perf_check) or
+    "device" (lc_perf_check_history)."""
+    pack = pack_of(opts)
     hist = history if isinstance(history, PerfHistory) else PerfHistory.from_ops(history)
+    if pack == "device":
+        checked = CheckedPerf(dev, hist, make_opts(opts))
+        return PerfSeries(checked, checked.results)
     packed = PackedPerf(hist)
     return PerfSeries(packed, check_batch(dev, packed.view, make_opts(opts)))
 
@@ -307,6 +378,7 @@ class PerfChecker:
 
     def __init__(self, opts: Optional[Dict] = None):
         self.opts = dict(opts or {})
+        self.pack = pack_of(self.opts)
         self.device = int(self.opts.get("device", 0))
         self.last: Optional[PerfSeries] = None
 
